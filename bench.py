@@ -20,15 +20,19 @@ end; the time reported is the max over ranks.
 Data: synthetic per-month summands of the production shape (no WRDS/JKP data exists here);
 random SPD denom_t = X_t'X_t / N with X_t ~ N(0,1) of shape 500 x 513 (S&P 500 universe).
 
-The same JSON line also carries the FULL grid-search wall-clock including the S4 input
-construction (``s4_s5_s6_wall_ms``: every PFML month's Barra Sigma, m_func, (24) Horner
+A plain run sets up, warms up, times ``--steps`` steps and prints the one JSON result line
+(``ms_per_step``: milliseconds per timed step); ``--dump-outputs DIR`` also writes what the
+last timed step returned as ``DIR/<name>.npy``.
+
+With ``--full`` the same JSON line also carries the FULL grid-search wall-clock including the
+S4 input construction (``s4_s5_s6_wall_ms``: every PFML month's Barra Sigma, m_func, (24) Horner
 chains and (25) summands for 2 distinct g on a synthetic 500-stock universe, then S5 + S6),
 timed the same way (barrier + synchronize on both sides, max over ranks).  Multi-GPU: each
 rank builds the S4 summands of the months it owns (``search.s4_compute_rows``: its burn-in
 pieces and hp-year blocks) and receives the one-block validation halo of its last year from
 the next rank by one all-gather (``search.complete_local_reals``) - every month's S4 runs
-once.  ``--no-inputs`` skips it; ``--with-inputs`` makes that full pipeline the timed step
-itself.
+once.  Without ``--full`` (or with ``--no-inputs``) it is skipped; ``--with-inputs`` makes
+that full pipeline the timed step itself.
 """
 from __future__ import annotations
 
@@ -248,6 +252,38 @@ def timed(fn, steps: int, warmup: int, dev) -> float:
     return 1000.0 * dt / max(1, steps)
 
 
+DUMP_BUDGET_BYTES = 48 * 2**20    # all --dump-outputs arrays together (float64)
+
+
+def dump_outputs(path: str, res, scores) -> dict:
+    """``--dump-outputs``: what the timed step handed back in its last run - the grid's
+    utilities ``obj`` with their validation months / hp years, the ridge coefficients ``beta``
+    of this rank's hp years, and per frame g the expanding-mean ``cum_g<g>`` and dense
+    ``rank_g<g>`` - one float64 ``<name>.npy`` each.  An array over its share of the budget is
+    saved as a fixed sample (sorted flat indices drawn from a generator seeded by the name and
+    the shape, so two builds sample the same elements; ``<name>`` then ends in ``_sample``)."""
+    import zlib
+    arrs = {"obj": res.obj, "beta": res.beta,
+            "val_months": torch.as_tensor(np.asarray(res.val_months)),
+            "val_year": torch.as_tensor(np.asarray(res.val_year))}
+    for g, (_, cum, rank) in enumerate(scores):
+        arrs[f"cum_g{g}"], arrs[f"rank_g{g}"] = cum, rank
+    cap = DUMP_BUDGET_BYTES // (8 * len(arrs))
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, t in arrs.items():
+        t = t.detach()
+        if t.numel() > cap:
+            rng = np.random.default_rng([zlib.crc32(name.encode()), *t.shape])
+            idx = np.sort(rng.integers(0, t.numel(), size=cap))
+            t = t.reshape(-1)[torch.as_tensor(idx, device=t.device)]
+            name += "_sample"
+        a = t.to(torch.float64).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def s4_stress(args) -> None:
     """BASELINE config 4 (3000-stock universe): per-month S4 cost at a large N (Barra Sigma,
     m_func with its 20+ N x N inversions, the (24) Horner chains over [S | I] of width
@@ -380,8 +416,16 @@ def main():
                          "= 0 and are repaired on the device (reported as 'repairs')")
     ap.add_argument("--dump", default="",
                     help="rank 0 saves the gathered utilities of the last step here (tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last one returned "
+                         "(utilities, ridge coefficients, cum_obj, rank) as DIR/<name>.npy, "
+                         "float64; the inputs are seeded, so two builds compare array by array")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement also time S4 alone and the full "
+                         "S4 + S5 + S6 grid search (s4_ms, s4_s5_s6_wall_ms, ... in the JSON line)")
     ap.add_argument("--no-inputs", action="store_true",
-                    help="skip the extra full (S4 + S5 + S6) wall-clock measurement")
+                    help="skip the extra full (S4 + S5 + S6) wall-clock measurement even with "
+                         "--full (the default without it)")
     ap.add_argument("--stocks", type=int, default=500)
     ap.add_argument("--precision", default="fp64", choices=["fp64", "fp32", "bf16", "fp8"],
                     help="with --with-inputs: S4 covariance / RFF / risk GEMMs in fp32, or on bf16 / "
@@ -458,8 +502,11 @@ def main():
     if args.dump and env.is_main:
         torch.save({"obj": res.obj.cpu(), "val_months": torch.as_tensor(res.val_months),
                     "val_year": torch.as_tensor(res.val_year)}, args.dump)
+    if args.dump_outputs and env.is_main:
+        dumped = dump_outputs(args.dump_outputs, res, box["scores"])
+        print(f"[bench] outputs of the last step: {dumped}", file=sys.stderr)
     full = None
-    if not args.with_inputs and not args.no_inputs:
+    if args.full and not args.with_inputs and not args.no_inputs:
         # the full grid-search wall-clock INCLUDING S4 (BASELINE.json's second metric)
         del reals
         if dev.type == "cuda":

@@ -222,7 +222,7 @@ def test_bench_contract_two_ranks_gloo(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-           "--tiny", "--device", "cpu"]
+           "--tiny", "--device", "cpu", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(tmp_path),
                        env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -237,6 +237,44 @@ def test_bench_contract_two_ranks_gloo(tmp_path):
         assert k in rec, k
     assert rec["n_gpus"] == 2 and rec["config"]["parallelism"] == "dp2"
     assert rec["value"] > 0 and rec["config"]["outputs_finite"]
+    assert rec["s4_s5_s6_wall_ms"] > 0 and rec["s4_outputs_finite"]          # --full
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain ``bench.py`` run times ``--steps`` steps and nothing else (no S4 + S5 + S6
+    measurement without ``--full``); ``--dump-outputs`` writes the last step's arrays as
+    float64 ``.npy`` files, identical from run to run (seeded inputs)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, OMP_NUM_THREADS="1", PYTHONPATH=root)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    out = {}
+    for tag in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1",
+                            "--steps", "2", "--warmup", "1", "--tiny", "--device", "cpu",
+                            "--dump-outputs", str(tmp_path / tag)],
+                           capture_output=True, text=True, timeout=600, env=env,
+                           cwd=str(tmp_path))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+        assert not [k for k in rec if k.startswith("s4_")], rec.keys()
+        d = tmp_path / tag
+        out[tag] = {n[:-4]: np.load(d / n) for n in sorted(os.listdir(d))}
+    a, b = out["a"], out["b"]
+    assert {"obj", "beta", "val_months", "val_year", "cum_g0", "rank_g0"} <= set(a)
+    assert a.keys() == b.keys()
+    assert a["obj"].shape == (len(a["val_months"]), 2, 2, 101)
+    for n in a:
+        assert a[n].dtype == np.float64 and np.isfinite(a[n]).all(), n
+        assert np.array_equal(a[n], b[n]), n
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2**20
 
 
 def test_bench_gpus_flag_spawns_ranks(tmp_path):

@@ -105,7 +105,7 @@ for step in ${MODE//,/ }; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
       rc=$?; tail -1 $OUT/smoke.log; if [ $rc -ne 0 ]; then exit $rc; fi ;;
     bench)
-      timeout -k 10 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+      timeout -k 10 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
       rc=$?; grep '^{' $OUT/bench.json | cut -c1-400; if [ $rc -ne 0 ]; then tail -5 $OUT/bench.err; exit $rc; fi ;;
     repair)
       # lambda = 0 repair load on the production grid: collinear summands (every window rank
