@@ -20,6 +20,19 @@
 // month.  Every workgroup writes a deterministic per-row-tile
 // partial; a second tiny kernel sums the partials in a fixed order (bitwise reproducible, no
 // float atomics).
+//
+// Forms (ops/ridge.py quad_launch picks one per launch):
+//  * quadform_pipe_kernel (default): the direct-A form below with a software-pipelined K
+//    loop for aligned tiles (main index count a multiple of 64: every production cell) -
+//    no branch, clamp or select around a load, counted vmcnt / lgkmcnt waits only, two B
+//    fragment register sets, no vector ALU work beside the 28 MFMAs of a step, and an
+//    epilogue whose loads go out in one batch.  Tiles that are not aligned go to
+//    quadform_rest_kernel, the direct form's loop, in a second launch.
+//  * quadform_direct_kernel (PFML_QUAD_DIRECT=1): the direct-A form for every tile.
+//  * quadform_kernel<1|2> (PFML_QUAD_DIRECT=0, PFML_QUAD_MM=1|2): D and beta staged in LDS.
+// The pipelined and the direct form add the same products in the same order (the diagonal
+// block's weight 1/2 is a power of two wherever it is applied), so barring underflow they
+// agree bitwise (they do on the benchmark's grid); the LDS-staged forms have their own k order.
 #include "common.h"
 #include <cstdlib>
 #include <type_traits>
@@ -245,11 +258,31 @@ __device__ __forceinline__ int qd_swz(int l) {
   return (m & 3) | ((m & 4) << 1);
 }
 
-__global__ __launch_bounds__(NT, 3) void quadform_direct_kernel(
-    const double* __restrict__ D, int64_t ldD, const double* __restrict__ R,
-    const double* __restrict__ Bt, int64_t ldB, const JobDesc* __restrict__ jobs,
-    const int* __restrict__ tile_job, int L, double* __restrict__ partial) {
-  __shared__ __attribute__((aligned(16))) double Bs[2][NCOL * BK];
+typedef double double2_t __attribute__((ext_vector_type(2)));
+
+// Aligned tiles: the main index count is a multiple of the 64-row tile (every production
+// cell: 64, 128, 256, 512), so every row of every row tile and every k of every K step is in
+// range, and the byte offsets into one D_t and one beta block fit 32 bits.
+__host__ __device__ __forceinline__ bool quad_aligned(int nfull, int L, int64_t ldD,
+                                                      int64_t ldB) {
+  return quad_main(nfull) % BM == 0 && nfull <= ldB && nfull <= ldD &&
+         (int64_t)nfull * ldD * 8 < (int64_t(1) << 31) &&
+         (int64_t)L * ldB * 8 < (int64_t(1) << 31);
+}
+
+// One body, three kernels.  QD_ALL: the direct form's loop for every tile.  QD_PIPE: the
+// pipelined loop for the aligned tiles of the launch, any other tile is left alone.
+// QD_REST: the direct form's loop for exactly the tiles QD_PIPE leaves (launched after it,
+// and only when the host's plan holds such a tile).  A tile's arithmetic depends on its own
+// job alone, so results do not depend on what else the launch holds.
+enum { QD_ALL = 0, QD_PIPE = 1, QD_REST = 2 };
+
+template <int MODE>
+__device__ __forceinline__ void quad_direct_body(
+    double (*Bs)[NCOL * BK], const double* __restrict__ D, int64_t ldD,
+    const double* __restrict__ R, const double* __restrict__ Bt, int64_t ldB,
+    const JobDesc* __restrict__ jobs, const int* __restrict__ tile_job, int L,
+    double* __restrict__ partial) {
   static_assert(NW * NCOL <= 2 * NCOL * BK, "cross-wave sums must fit in the beta buffers");
   double (*red)[NCOL] = reinterpret_cast<double (*)[NCOL]>(&Bs[0][0]);
 
@@ -298,6 +331,130 @@ __global__ __launch_bounds__(NT, 3) void quadform_direct_kernel(
   };
 
   const int nst = (n - i0 + BK - 1) / BK;          // K steps of this row tile
+  if constexpr (MODE != QD_ALL) {
+    if (quad_aligned(nfull, L, ldD, ldB) != (MODE == QD_PIPE)) return;   // not this kernel's
+  }
+  if constexpr (MODE == QD_PIPE) {
+    // Pipelined loop (nst is a multiple of 4, >= 4).  No clamp, select or branch sits around
+    // a load: D and beta come through one buffer resource each, a loop-invariant 32-bit
+    // offset per element in a VGPR and the step's k offset in an SGPR, clamped to the last
+    // K tile - the two steps past the end load that tile again and nobody reads it.  The
+    // D ring has four slots so that slot and LDS buffer are compile-time constants of a
+    // loop unrolled by four; D is loaded two steps ahead, after the next step's beta, so
+    // the counted wait for beta at the end of a step leaves it in flight.  The B fragments
+    // of a k-slice sit in one of two register sets: slice s + 1 is read from LDS while
+    // slice s's MFMAs issue.  The diagonal block's weight 1/2 is applied to the accumulators
+    // once, after the block's four steps (exact: a power of two).
+    const int dbytes = (int)(((int64_t)(nfull - 1) * ldD + nfull) * 8);
+    const int bbytes = (int)(((int64_t)(L - 1) * ldB + nfull) * 8);
+    const __amdgpu_buffer_rsrc_t rsD =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(Dm), 0, dbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsB =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(bt), 0, bbytes, 0x00020000);
+    const int dvo = ((i0 + w * 16 + r) * (int)ldD + 4 * c) * 8;
+    int bvo[BQ];
+#pragma unroll
+    for (int q = 0; q < BQ; ++q) bvo[q] = (min((t >> 4) + 16 * q, L - 1) * (int)ldB + (t & 15)) * 8;
+    // LDS element of this thread's staged beta (row t / 16 + 16 q: same swizzle for every
+    // q) and of its fragment of slice s (row 16 q + r); both + 256 q
+    const int bso = (t >> 4) * BK + ((t & 15) ^ qd_swz(t >> 4));
+    int fro[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) fro[s] = r * BK + ((4 * c + s) ^ swz);
+    const int klast = (n - BK) * 8;                // byte offset of the last K tile
+    double fa[4][4], fr[BQ];
+    auto fdload = [&](int slot, int kb) {
+      const double2_t lo = __builtin_bit_cast(
+          double2_t, __builtin_amdgcn_raw_buffer_load_b128(rsD, dvo, kb, 0));
+      const double2_t hi = __builtin_bit_cast(
+          double2_t, __builtin_amdgcn_raw_buffer_load_b128(rsD, dvo + 16, kb, 0));
+      fa[slot][0] = lo[0]; fa[slot][1] = lo[1]; fa[slot][2] = hi[0]; fa[slot][3] = hi[1];
+    };
+    auto fbload = [&](int kb) {
+#pragma unroll
+      for (int q = 0; q < BQ; ++q)
+        fr[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rsB, bvo[q], kb, 0));
+    };
+    auto fbstore = [&](int buf) {
+#pragma unroll
+      for (int q = 0; q < BQ; ++q) Bs[buf][q * 256 + bso] = fr[q];
+    };
+    auto fstep = [&](auto slot_c, int kb) {
+      constexpr int cur = decltype(slot_c)::value;
+      constexpr int buf = cur & 1;
+      fbload(min(kb + BK * 8, klast));
+      fdload((cur + 2) & 3, min(kb + 2 * BK * 8, klast));
+      double fb[2][NTILE];
+#pragma unroll
+      for (int q = 0; q < NTILE; ++q) fb[0][q] = Bs[buf][q * 256 + fro[0]];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        if (s < 3) {
+#pragma unroll
+          for (int q = 0; q < NTILE; ++q) fb[(s + 1) & 1][q] = Bs[buf][q * 256 + fro[s + 1]];
+        }
+#pragma unroll
+        for (int q = 0; q < NTILE; ++q) acc[q] = mfma_f64_16x16x4(fa[cur][s], fb[s & 1][q], acc[q]);
+      }
+      fbstore(buf ^ 1);
+      __syncthreads();
+    };
+    const int kb0 = i0 * 8, kend = n * 8;
+    fbload(kb0);
+    fdload(0, kb0);
+    fdload(1, kb0 + BK * 8);
+    fbstore(0);
+    __syncthreads();
+    // every step stages and syncs, the last one included (it stages the clamped tile for
+    // nobody): with the last step's staging under a branch the compiler sinks its beta loads
+    // into that branch and waits for them there in full, once per four steps
+    for (int kb = kb0; kb < kend; kb += 4 * BK * 8) {
+      fstep(std::integral_constant<int, 0>{}, kb);
+      fstep(std::integral_constant<int, 1>{}, kb + BK * 8);
+      fstep(std::integral_constant<int, 2>{}, kb + 2 * BK * 8);
+      fstep(std::integral_constant<int, 3>{}, kb + 3 * BK * 8);
+      if (kb == kb0) {
+#pragma unroll
+        for (int q = 0; q < NTILE; ++q) acc[q] *= 0.5;
+      }
+    }
+    __syncthreads();                               // red reuses Bs
+    // Tail column and epilogue as below, but every row is in range here, so all their
+    // loads (r_i, beta_l[i], beta_l[n], D[i][n]) are issued unconditionally in one batch
+    // (under `if (gi < n && l < L)` each of the 28 products waited for its own loads: 28
+    // memory round trips in a row, more than the whole K loop of a 4-step tile).  Columns
+    // l >= L compute on row L - 1's beta; nobody reads their sums.
+    auto grow = [&](int rr) { return i0 + w * 16 + PFML_F64_CROW(lane, rr); };
+    const int tn = (tail ? n : n - 1) * 8;         // in range either way; used if tail
+    double er[4], td[4], eb[NTILE][4], tb[NTILE];
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      er[rr] = rm[grow(rr)];
+      td[rr] = __builtin_bit_cast(
+          double, __builtin_amdgcn_raw_buffer_load_b64(rsD, grow(rr) * (int)ldD * 8, tn, 0));
+    }
+#pragma unroll
+    for (int q = 0; q < NTILE; ++q) {
+      const int lo = min(q * 16 + r, L - 1) * (int)ldB * 8;
+      tb[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rsB, lo, tn, 0));
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr)
+        eb[q][rr] = __builtin_bit_cast(
+            double, __builtin_amdgcn_raw_buffer_load_b64(rsB, lo + grow(rr) * 8, 0, 0));
+    }
+#pragma unroll
+    for (int q = 0; q < NTILE; ++q) {
+      double s = 0.0;
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const double u = tail ? fma(td[rr], tb[q], acc[q][rr]) : acc[q][rr];
+        s += eb[q][rr] * (er[rr] - u);               // u = U / 2
+      }
+      s += __shfl_xor(s, 16, 64);
+      s += __shfl_xor(s, 32, 64);
+      if (lane < 16) red[w][q * 16 + r] = s;
+    }
+  } else {
   bload(i0);
   dload(0, i0);
   if (nst > 1) dload(1, i0 + BK);
@@ -363,6 +520,7 @@ __global__ __launch_bounds__(NT, 3) void quadform_direct_kernel(
     s += __shfl_xor(s, 32, 64);
     if (lane < 16) red[w][l] = s;
   }
+  }
   __syncthreads();
   if (t < L) {
     double s = 0.0;
@@ -370,6 +528,32 @@ __global__ __launch_bounds__(NT, 3) void quadform_direct_kernel(
     for (int q = 0; q < NW; ++q) s += red[q][t];
     partial[(int64_t)(jd.ptile0 + rt) * L + t] = s;
   }
+}
+
+__global__ __launch_bounds__(NT, 3) void quadform_direct_kernel(
+    const double* __restrict__ D, int64_t ldD, const double* __restrict__ R,
+    const double* __restrict__ Bt, int64_t ldB, const JobDesc* __restrict__ jobs,
+    const int* __restrict__ tile_job, int L, double* __restrict__ partial) {
+  __shared__ __attribute__((aligned(16))) double Bs[2][NCOL * BK];
+  quad_direct_body<QD_ALL>(Bs, D, ldD, R, Bt, ldB, jobs, tile_job, L, partial);
+}
+
+// (4 waves per SIMD - 128 VGPRs, the epilogue batch spilling 7 doubles - measured no faster:
+// profiles/r07_experiments.md)
+__global__ __launch_bounds__(NT, 3) void quadform_pipe_kernel(
+    const double* __restrict__ D, int64_t ldD, const double* __restrict__ R,
+    const double* __restrict__ Bt, int64_t ldB, const JobDesc* __restrict__ jobs,
+    const int* __restrict__ tile_job, int L, double* __restrict__ partial) {
+  __shared__ __attribute__((aligned(16))) double Bs[2][NCOL * BK];
+  quad_direct_body<QD_PIPE>(Bs, D, ldD, R, Bt, ldB, jobs, tile_job, L, partial);
+}
+
+__global__ __launch_bounds__(NT, 3) void quadform_rest_kernel(
+    const double* __restrict__ D, int64_t ldD, const double* __restrict__ R,
+    const double* __restrict__ Bt, int64_t ldB, const JobDesc* __restrict__ jobs,
+    const int* __restrict__ tile_job, int L, double* __restrict__ partial) {
+  __shared__ __attribute__((aligned(16))) double Bs[2][NCOL * BK];
+  quad_direct_body<QD_REST>(Bs, D, ldD, R, Bt, ldB, jobs, tile_job, L, partial);
 }
 
 __global__ void quadform_reduce_kernel(const double* __restrict__ partial,
@@ -398,17 +582,30 @@ __global__ void quadform_reduce_kernel(const double* __restrict__ partial,
 extern "C" int pfml_quadform_job_desc_size() { return (int)sizeof(JobDesc); }
 extern "C" int pfml_quadform_rows_per_tile() { return BM; }
 extern "C" int pfml_quadform_row_tiles(int n) { return (quad_main(n) + BM - 1) / BM; }
+// whether the tiles of a job of n indices take the pipelined loop (the kernels' own test)
+extern "C" int pfml_quadform_aligned(int n, int L, int64_t ldD, int64_t ldB) {
+  return quad_aligned(n, L, ldD, ldB) ? 1 : 0;
+}
 
-// tile_job: mm (1 or 2; 1 for the direct form, mm = 3) int32 entries per tile.
+// tile_job: mm (1 or 2; 1 for the direct and pipelined forms, mm = 3 / 4 / 5) int32 entries
+// per tile.
 extern "C" hipError_t pfml_quadform(const double* D, int64_t ldD, const double* R,
                                     const double* Bt, int64_t ldB, const void* jobs, int njobs,
                                     const int* tile_job, int ntiles, int mm, int L,
                                     double* partial, double* obj, hipStream_t st) {
   if (njobs <= 0) return hipSuccess;
-  // mm: months per tile (1 / 2); 3 = the direct-A form on the one-month tile list
-  if (L > NCOL || mm < 1 || mm > 3) return hipErrorInvalidValue;
+  // mm: months per tile (1 / 2); 3 = the direct-A form on the one-month tile list; 4 = the
+  // pipelined form, every job of the launch aligned (pfml_quadform_aligned); 5 = the
+  // pipelined form for the aligned jobs and the direct form's loop for the rest
+  if (L > NCOL || mm < 1 || mm > 5) return hipErrorInvalidValue;
   const JobDesc* jd = static_cast<const JobDesc*>(jobs);
-  if (mm == 3)
+  if (mm >= 4) {
+    hipLaunchKernelGGL(quadform_pipe_kernel, dim3(ntiles), dim3(NT), 0, st, D, ldD, R, Bt, ldB,
+                       jd, tile_job, L, partial);
+    if (mm == 5)
+      hipLaunchKernelGGL(quadform_rest_kernel, dim3(ntiles), dim3(NT), 0, st, D, ldD, R, Bt,
+                         ldB, jd, tile_job, L, partial);
+  } else if (mm == 3)
     hipLaunchKernelGGL(quadform_direct_kernel, dim3(ntiles), dim3(NT), 0, st, D, ldD, R, Bt, ldB,
                        jd, tile_job, L, partial);
   else if (mm == 2)

@@ -829,12 +829,24 @@ def quad_launch(plan: dict, d_desc: torch.Tensor, d_tj: torch.Tensor, D: torch.T
     L, Pb = beta.shape[1], beta.shape[2]
     nt = plan["ntiles"]
     partial = torch.empty((plan["nslots"], L), dtype=torch.float64, device=D.device)
-    # one-month tiles take the direct-A form (csrc/quadform.hip quadform_direct_kernel: D
-    # fragments straight to registers two steps ahead, only beta through LDS) unless
-    # PFML_QUAD_DIRECT=0
+    # one-month tiles take the direct-A form (csrc/quadform.hip: D fragments straight to
+    # registers two steps ahead, only beta through LDS), by default with the pipelined loop
+    # for the aligned jobs (quadform_pipe_kernel: mm = 4 when every job of the launch is
+    # aligned, as in production; else mm = 5, which adds a launch of the direct form's loop
+    # for the rest).  PFML_QUAD_DIRECT=1 selects the direct form for every tile
+    # (quadform_direct_kernel, mm = 3), PFML_QUAD_DIRECT=0 the LDS-staged form.
     mm = plan["mm"]
-    if mm == 1 and os.environ.get("PFML_QUAD_DIRECT", "1") != "0":
-        mm = 3
+    if mm == 1:
+        direct = os.environ.get("PFML_QUAD_DIRECT", "")
+        if direct == "":
+            key = ("aligned", L, P, Pb)
+            if key not in plan:
+                lib = nat.hip_lib()
+                plan[key] = all(lib.pfml_quadform_aligned(int(v), L, P, Pb)
+                                for v in np.unique(plan["desc"]["n"]))
+            mm = 4 if plan[key] else 5
+        elif direct != "0":
+            mm = 3
     nat.check(nat.hip_lib().pfml_quadform(D.data_ptr(), P, R.data_ptr(), beta.data_ptr(), Pb,
                                           d_desc.data_ptr(), plan["nj"], d_tj.data_ptr(), nt,
                                           mm, L,

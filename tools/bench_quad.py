@@ -1,17 +1,18 @@
 #!/usr/bin/env python3
 """Validation-utility kernel (csrc/quadform.hip) in isolation, at the headline shapes:
 12 validation months x 106 (g, year) cells for each p (n = 513 / 257 / 129 / 65), 101 lambdas.
-Prints ms per launch and the achieved fp64 rate (symmetric half of D_t B counted)."""
+Prints ms per launch and the achieved fp64 rate (symmetric half of D_t B counted).  The launch
+plan is made and uploaded once, as in a grid step, and the launches are timed with device
+events: host planning (about 2 ms per call of quadform_utilities) is not the kernel's time."""
 import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pfml.ops.ridge import quadform_utilities  # noqa: E402
+from pfml.ops.ridge import quad_launch, quad_plan, upload  # noqa: E402
 
 
 def main():
@@ -27,14 +28,20 @@ def main():
         jc = np.repeat(np.arange(C), 12)
         jm = (np.arange(C * 12) * 7) % T
         jn = np.full(C * 12, n)
-        quadform_utilities(D, R, beta, jc, jm, jn)
+        plan = quad_plan(P, L, P, jc, jm, jn)
+        d_desc, d_tj = upload([plan["desc"], plan["tile_job"]], dev)
+        obj = torch.empty((len(jc), L), dtype=torch.float64, device=dev)
+        for _ in range(3):
+            quad_launch(plan, d_desc, d_tj, D, R, beta, obj)
         torch.cuda.synchronize()
-        reps = 5
-        t = time.perf_counter()
+        reps = 20
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
         for _ in range(reps):
-            quadform_utilities(D, R, beta, jc, jm, jn)
+            quad_launch(plan, d_desc, d_tj, D, R, beta, obj)
+        e1.record()
         torch.cuda.synchronize()
-        ms = (time.perf_counter() - t) / reps * 1e3
+        ms = e0.elapsed_time(e1) / reps
         flops = len(jc) * (n * n + n * 64) * 101 * 2 / 2      # upper block triangle
         out[f"n{n}_ms"] = round(ms, 3)
         out[f"n{n}_tflops"] = round(flops / ms / 1e9, 1)
