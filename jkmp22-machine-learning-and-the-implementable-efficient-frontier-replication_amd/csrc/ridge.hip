@@ -7,8 +7,11 @@
 //
 //     beta_l = Q (T + l I)^-1 Q^T rbar
 //
-// Used for 528 < n <= 1024 (p up to 1023; the band path, ridge_band.hip, takes n <= 528).
-// One 1024-thread workgroup owns one (g, year, p) cell.
+// Used for 528 < n <= 2049 (p up to 2048; the band path, ridge_band.hip, takes n <= 528).
+// One 1024-thread workgroup owns one (g, year, p) cell.  The kernels that keep per-row vectors
+// in LDS are templates on that capacity: CAP = 1024 for launches with n <= 1024 and CAP = 2112
+// (2049 rounded up to whole 64-column blocks) for 1024 < n <= 2049, picked per launch by its
+// largest n.  Phase B keeps nothing in LDS and is shared.
 //
 // Phase A (tridiagonalisation, blocked as LAPACK dlatrd: ridge_tridiag_blocked_kernel).  The
 //   n x n working copy lives in global memory (L2-resident) in FULL symmetric storage; within
@@ -17,16 +20,22 @@
 // Phase B (lambda sweep).  One thread per lambda runs Gaussian elimination with partial
 //   pivoting on T + l I (as LAPACK dgtsv), so l = 0 on a singular-ish Dbar behaves like the
 //   reference's pivoted LU; the back-substitution prefetches its operands 8 rows ahead.
-// Phase C (back-transform).  Y = [y_l] (n x L) is held in REGISTERS (thread = (lambda, row
-//   part), rows strided over parts), reflectors are staged through a 3-deep LDS ring, one
-//   barrier per reflector.
+// Phase C (back-transform).  n <= 528: Y = [y_l] (n x L) is held in REGISTERS (thread =
+//   (lambda, row part), rows strided over parts), reflectors are staged through a 3-deep LDS
+//   ring, one barrier per reflector.  528 < n <= 1024: Y stays in global memory and the
+//   reflectors are applied one at a time.  n > 1024: compact-WY blocks of 16 reflectors on the
+//   fp64 MFMA, one workgroup per (cell, 16 lambdas), Y in registers
+//   (ridge_backtransform_wy_kernel; measured 12-34x faster than the one-at-a-time form at
+//   n = 1025 and 2049, profiles/r08_large_p.json).
 #include "common.h"
 #include "ridge_desc.h"
 #include <cstdlib>
 
 namespace {
 
-constexpr int NMAX = 1024;      // largest n = p + 1 supported
+constexpr int CAP_S = 1024;     // LDS vector capacity of the n <= 1024 instances
+constexpr int CAP_L = 2112;     // ... of the 1024 < n <= 2049 instances
+constexpr int NMAX = 2049;      // largest n = p + 1 supported
 constexpr int NT = 1024;        // threads per workgroup
 constexpr int NW = NT / 64;
 constexpr int YREG = 33;        // rows of Y per lane in the register back-transform (n <= 528)
@@ -46,12 +55,13 @@ typedef RidgeCellDesc CellDesc;
 // (VW[i][0..PB) = V, VW[i][PB..2PB) = W) so correction dots are coalesced.
 constexpr int PB = 16;
 
+template <int CAP>
 __global__ __launch_bounds__(NT) void ridge_tridiag_blocked_kernel(
     const double* __restrict__ SD, int64_t ldS, const double* __restrict__ Sr,
     const CellDesc* __restrict__ cells, int L, double* __restrict__ work) {
-  __shared__ double v[NMAX], pk[NMAX], z[NMAX];
-  __shared__ double dd[NMAX], ee[NMAX], tau[NMAX];
-  __shared__ double part[NT];
+  __shared__ double v[CAP], pk[CAP], z[CAP];
+  __shared__ double dd[CAP], ee[CAP], tau[CAP];
+  __shared__ double part[CAP > NT ? CAP : NT];
   __shared__ double red[NW * 2];
   __shared__ double red32[32][33];
   __shared__ double xy[2 * PB], vwk[2 * PB];
@@ -136,8 +146,33 @@ __global__ __launch_bounds__(NT) void ridge_tridiag_blocked_kernel(
       //     + correction dots  V'v, W'v  (q < j)
       const int r0 = k + 1, m = n - r0;
       const int ncb = (m + 63) >> 6;
-      const int nrg = NW / ncb;
-      {
+      // more column blocks than waves (m > 1024, CAP_L only): every wave sweeps all rows of
+      // column blocks wid, wid + NW, ...
+      const bool wide = CAP > NT && ncb > NW;
+      const int nrg = wide ? 1 : NW / ncb;
+      if (wide) {
+        for (int cb = wid; cb < ncb; cb += NW) {
+          const int c = cb * 64 + lane;
+          const int i = r0 + c;
+          double acc0 = 0.0, acc1 = 0.0;
+          if (i < n) {
+            const double* col = A + i;
+            int l = r0;
+            for (; l + 16 <= n; l += 16) {
+              double a[16];
+#pragma unroll
+              for (int u = 0; u < 16; ++u) a[u] = col[(int64_t)(l + u) * n];
+#pragma unroll
+              for (int u = 0; u < 16; u += 2) {
+                acc0 += a[u] * v[l + u];
+                acc1 += a[u + 1] * v[l + u + 1];
+              }
+            }
+            for (; l < n; ++l) acc0 += col[(int64_t)l * n] * v[l];
+          }
+          part[c] = acc0 + acc1;
+        }
+      } else {
         const int cb = wid % ncb, rg = wid / ncb;
         if (rg < nrg) {
           const int c = cb * 64 + lane;
@@ -317,12 +352,16 @@ __global__ __launch_bounds__(256) void ridge_trisolve_kernel(
 }
 
 // Phase C: back-transform, one 1024-thread workgroup per cell.
+template <int CAP>
 __global__ __launch_bounds__(NT) void ridge_backtransform_kernel(
     const CellDesc* __restrict__ cells, int L, double* __restrict__ work,
-    double* __restrict__ beta_out, int64_t ldo) {
-  __shared__ double tau[NMAX];
+    double* __restrict__ beta_out, int64_t ldo, int n_skip) {
+  __shared__ double tau[CAP];
   const CellDesc cd = cells[blockIdx.x];
   const int n = cd.n;
+  // (large launches: cells above n_skip are the blocked kernel's, ridge_backtransform_wy_kernel)
+  if constexpr (CAP > CAP_S)
+    if (n > n_skip) return;
   const int t = threadIdx.x, lane = t & 63;
   const int wid = __builtin_amdgcn_readfirstlane(t >> 6);   // wave-uniform row part
   double* A = work + cd.work;
@@ -425,7 +464,7 @@ __global__ __launch_bounds__(NT) void ridge_backtransform_kernel(
   }
   // Generic path (n > NW * YREG): Y stays in global memory.
   {
-    __shared__ double vbuf[NMAX];
+    __shared__ double vbuf[CAP];
     __shared__ double pr[8][128];
     const int lcol = t & 127, prt = t >> 7;
     for (int k = n - 3; k >= 0; --k) {
@@ -449,6 +488,157 @@ __global__ __launch_bounds__(NT) void ridge_backtransform_kernel(
   for (int64_t e = t; e < (int64_t)L * n; e += NT) {
     const int l = (int)(e / n), i = (int)(e % n);
     out[(int64_t)l * ldo + i] = Y[(int64_t)i * L + l];
+  }
+}
+
+// Phase C for n > 1024: blocked (compact WY) back-transform on the fp64 MFMA.  The generic path
+// above makes n - 2 read-modify-write passes over Y; here the reflectors go in blocks of WB = 16
+// consecutive ones,  H_k0 .. H_k0+15 = I - V T V'  (T upper triangular, LAPACK dlarft forward /
+// column-wise from the Gram matrix V'V), and a block costs
+//     [G | W] = V' [V | Y]   (16 x m by m x 16, v_mfma_f64_16x16x4 over the rows)
+//     W <- T W               (16 x 16, LDS)
+//     Y <- Y - V W           (m x 16 by 16 x 16 per 16-row tile)
+// The lambda columns are independent: workgroup (cell, chunk) owns the WLC = 16 columns
+// [16 chunk, 16 chunk + 16) of its cell and keeps its n x 16 slice of Y in REGISTERS for the
+// whole sweep, in the MFMA accumulator layout (wave w owns the 16-row tiles w, w + 16, ...).
+// Register r of a tile is then at once the B operand of rows 4r .. 4r + 3 for V'Y and the
+// accumulator of Y - V W, so Y never moves.  Nothing is shared between workgroups (each
+// rebuilds the cell's T), the summation order is fixed by (n, row tile), and a cell's bits
+// depend on neither L nor the other cells of the launch.
+constexpr int WB = 16;          // reflectors per block
+constexpr int WLC = 16;         // lambdas per workgroup
+
+template <int CAP>
+__global__ __launch_bounds__(NT) void ridge_backtransform_wy_kernel(
+    const CellDesc* __restrict__ cells, int L, int nchunk, int n_above,
+    double* __restrict__ work, double* __restrict__ beta_out, int64_t ldo) {
+  constexpr int NTILE = ((CAP + 15) / 16 + NW - 1) / NW;    // 16-row tiles per wave
+  __shared__ double part[NW][2 * WB * 16];                  // per wave [G | W] partials
+  __shared__ double red[2 * WB * 16];
+  __shared__ double Tm[WB][WB + 1];
+  __shared__ double Wf[WB * WLC];
+  const int cell = blockIdx.x / nchunk, chunk = blockIdx.x % nchunk;
+  const CellDesc cd = cells[cell];
+  const int n = cd.n;
+  if (n <= n_above || n > CAP) return;                      // (the generic kernel's cells)
+  const int t = threadIdx.x, lane = t & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int c16 = lane & 15, g4 = lane >> 4;
+  const double* A = work + cd.work;
+  const double* Y = A + (int64_t)n * n;
+  const double* tg = Y + 5LL * n * L + 2 * n;
+  double* out = beta_out + cd.out;
+  const int l0 = chunk * WLC;
+  const int l = l0 + c16;
+  const bool lv = l < L;
+  // padding columns [n, ldo) of this chunk's lambda rows are zero
+  {
+    const int nl = min(WLC, L - l0);
+    const int64_t pad = ldo - n;
+    for (int64_t e = t; e < nl * pad; e += NT) out[(l0 + e / pad) * ldo + n + e % pad] = 0.0;
+  }
+  double4_t y[NTILE];
+#pragma unroll
+  for (int tt = 0; tt < NTILE; ++tt) {
+    const int base = (wid + NW * tt) * 16;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = base + 4 * r + g4;
+      y[tt][r] = (lv && row < n) ? Y[(int64_t)row * L + l] : 0.0;
+    }
+  }
+  const int nr = n - 2;                                     // reflectors k = 0 .. n-3
+  for (int b = (nr + WB - 1) / WB - 1; b >= 0; --b) {
+    const int k0 = b * WB;
+    const int nb = min(WB, nr - k0);
+    // [G | W] = V' [V | Y]: reflector k is row k of A, nonzero in rows (columns of A) > k
+    {
+      double4_t g = {0.0, 0.0, 0.0, 0.0}, w = {0.0, 0.0, 0.0, 0.0};
+      // (loads unconditional from clamped in-range addresses, masked after: no branches)
+      const int kq = k0 + c16;
+      const double* vrow = A + (int64_t)min(kq, nr - 1) * n;
+      // (opaque per block: the 36 row offsets are recomputed here, not hoisted out of the
+      // block loop into registers the Y tiles need)
+      int rb = wid * 16 + g4;
+      asm volatile("" : "+v"(rb));
+#pragma unroll
+      for (int tt = 0; tt < NTILE; ++tt) {
+        const int base = (wid + NW * tt) * 16;
+        if (base < n && base + 15 > k0) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = rb + NW * 16 * tt + 4 * r;
+            const double v = vrow[min(row, n - 1)];
+            const double a = (c16 < nb && row > kq && row < n) ? v : 0.0;
+            g = mfma_f64_16x16x4(a, a, g);
+            w = mfma_f64_16x16x4(a, y[tt][r], w);
+          }
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        part[wid][PFML_F64_CROW(lane, r) * 16 + c16] = g[r];
+        part[wid][WB * 16 + PFML_F64_CROW(lane, r) * 16 + c16] = w[r];
+      }
+    }
+    __syncthreads();
+    if (t < 2 * WB * 16) {
+      double s = 0.0;
+#pragma unroll
+      for (int q = 0; q < NW; ++q) s += part[q][t];
+      red[t] = s;
+    }
+    __syncthreads();
+    if (t < WB) {
+      // row t of T:  T[j][j] = tau_j,  T[0:j, j] = -tau_j T[0:j, 0:j] G[0:j, j]
+      // (rolled loops over the thread's own LDS row: unrolled, the 120 operand loads are
+      // hoisted into registers the Y tiles need)
+#pragma unroll 1
+      for (int j = 0; j < WB; ++j) {
+        const double tj = (j < nb) ? tg[k0 + j] : 0.0;
+        double s = 0.0;
+#pragma unroll 1
+        for (int q = t; q < j; ++q) s += Tm[t][q] * red[q * 16 + j];
+        Tm[t][j] = (j < t) ? 0.0 : (j == t ? tj : -tj * s);
+      }
+    }
+    __syncthreads();
+    if (t < WB * WLC) {
+      const int i = t >> 4, j = t & 15;
+      double s = 0.0;
+#pragma unroll
+      for (int q = 0; q < WB; ++q) s += Tm[i][q] * red[WB * 16 + q * 16 + j];
+      Wf[t] = s;
+    }
+    __syncthreads();
+    // Y <- Y - V W
+    int rc = wid * 16 + c16;
+    asm volatile("" : "+v"(rc));
+#pragma unroll
+    for (int tt = 0; tt < NTILE; ++tt) {
+      const int base = (wid + NW * tt) * 16;
+      if (base < n && base + 15 > k0) {
+        const int row = rc + NW * 16 * tt;
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+          const int q = 4 * s4 + g4;
+          const double v = A[(int64_t)min(k0 + q, nr - 1) * n + min(row, n - 1)];
+          const double a = (q < nb && row > k0 + q && row < n) ? -v : 0.0;
+          y[tt] = mfma_f64_16x16x4(a, Wf[q * WLC + c16], y[tt]);
+        }
+      }
+    }
+  }
+  if (lv) {
+#pragma unroll
+    for (int tt = 0; tt < NTILE; ++tt) {
+      const int base = (wid + NW * tt) * 16;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = base + 4 * r + g4;
+        if (row < n) out[(int64_t)l * ldo + row] = y[tt][r];
+      }
+    }
   }
 }
 
@@ -477,10 +667,22 @@ static long long* g_ridge_timing = nullptr;
 // Debug: per-cell phase cycle counters of the band reduction (tools/bench_ridge.py --timing).
 extern "C" void pfml_ridge_set_timing(long long* buf) { g_ridge_timing = buf; }
 
+static int g_bt_wy = 1;
+// A/B switch of the back-transform of cells with n > 1024 for later launches: 1 (default) the
+// blocked MFMA kernel, 0 the one-reflector-at-a-time generic path (tools/bench_large_p.py).
+extern "C" void pfml_ridge_set_bt_wy(int on) { g_bt_wy = on ? 1 : 0; }
+
+static int g_phases = 7;
+// Debug: phases of the tridiagonal path that later launches queue (bit 0 tridiagonalisation,
+// bit 1 tridiagonal solves, bit 2 back-transform; default all).  tools/bench_large_p.py times
+// one phase at a time between event pairs; a launch with phases left out computes nothing
+// useful.
+extern "C" void pfml_ridge_set_phases(int mask) { g_phases = mask & 7; }
+
 // n <= 528: the band path (ridge_band.hip: cooperative reduction, banded Cholesky, in-band
 // pivoted-LU repair of non-SPD lambdas through lu_list / lu_count / lu_cap, nullptr = off);
-// 528 < n <= 1024: the blocked tridiagonal path below, whose NaN markers go to the dense
-// repair (ridge_repair.hip).
+// 528 < n <= 2049: the blocked tridiagonal path below (the CAP_S instances for a launch with
+// nmax <= 1024, else CAP_L), whose NaN markers go to the dense repair (ridge_repair.hip).
 extern "C" hipError_t pfml_ridge_grid(const double* SD, int64_t ldS, const double* Sr,
                                       const void* cells, int ncells, int nmax,
                                       const double* lvec, int L, double* work, double* beta_out,
@@ -494,13 +696,35 @@ extern "C" hipError_t pfml_ridge_grid(const double* SD, int64_t ldS, const doubl
     return pfml_ridge_band_launch(SD, ldS, Sr, cells, ncells, lvec, L, work, beta_out, ldo,
                                   g_ridge_timing, lu_list, lu_count, lu_cap, wgmap, nwg, syncw,
                                   n_host, st);
-  hipLaunchKernelGGL(ridge_tridiag_blocked_kernel, dim3(ncells), dim3(NT), 0, st, SD, ldS, Sr,
-                     cd, L, work);
+  const bool large = nmax > CAP_S;
+  if (!(g_phases & 1)) {
+  } else if (large)
+    hipLaunchKernelGGL(ridge_tridiag_blocked_kernel<CAP_L>, dim3(ncells), dim3(NT), 0, st, SD,
+                       ldS, Sr, cd, L, work);
+  else
+    hipLaunchKernelGGL(ridge_tridiag_blocked_kernel<CAP_S>, dim3(ncells), dim3(NT), 0, st, SD,
+                       ldS, Sr, cd, L, work);
   const int64_t nth = (int64_t)ncells * L;
-  hipLaunchKernelGGL(ridge_trisolve_kernel, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0,
-                     st, cd, ncells, lvec, L, work);
-  hipLaunchKernelGGL(ridge_backtransform_kernel, dim3(ncells), dim3(NT), 0, st, cd, L, work,
-                     beta_out, ldo);
+  if (g_phases & 2)
+    hipLaunchKernelGGL(ridge_trisolve_kernel, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0,
+                       st, cd, ncells, lvec, L, work);
+  if (!(g_phases & 4)) {
+  } else if (large) {
+    // cells with n > 1024 on the blocked back-transform (one workgroup per 16 lambdas), the
+    // launch's smaller cells on the kernel they have in a small launch; each kernel's
+    // workgroups leave the other's cells at once
+    const int n_skip = g_bt_wy ? CAP_S : NMAX;
+    hipLaunchKernelGGL(ridge_backtransform_kernel<CAP_L>, dim3(ncells), dim3(NT), 0, st, cd, L,
+                       work, beta_out, ldo, n_skip);
+    if (g_bt_wy) {
+      const int nchunk = (L + WLC - 1) / WLC;
+      hipLaunchKernelGGL(ridge_backtransform_wy_kernel<CAP_L>, dim3(ncells * nchunk), dim3(NT),
+                         0, st, cd, L, nchunk, n_skip, work, beta_out, ldo);
+    }
+  } else {
+    hipLaunchKernelGGL(ridge_backtransform_kernel<CAP_S>, dim3(ncells), dim3(NT), 0, st, cd, L,
+                       work, beta_out, ldo, NMAX);
+  }
   return hipGetLastError();
 }
 

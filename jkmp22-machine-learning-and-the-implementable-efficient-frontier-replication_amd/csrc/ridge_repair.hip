@@ -139,18 +139,30 @@ __global__ __launch_bounds__(RT) void ridge_lu_repair_kernel(
 
 extern "C" int pfml_ridge_repair_wg() { return REPAIR_WG; }
 
-// workgroups of one repair launch: never more than the systems it can be handed (cap)
-static int repair_wgs(int cap) { return cap < REPAIR_WG ? (cap > 0 ? cap : 1) : REPAIR_WG; }
+// scratch ceiling: what REPAIR_WG systems of nmax = 1025 take (540 MB)
+constexpr int64_t SCRATCH_MAX = (int64_t)REPAIR_WG * 1025 * 1026;
+
+// workgroups of one repair launch: never more than the systems it can be handed (cap), and
+// above nmax = 1025 only as many as fit the scratch ceiling (16 at nmax = 2049); the kernel
+// walks the list with a grid stride, so fewer workgroups solve the same systems in turn
+static int repair_wgs(int cap, int nmax) {
+  int wg = cap < REPAIR_WG ? (cap > 0 ? cap : 1) : REPAIR_WG;
+  if (nmax > 1025) {
+    const int64_t fit = SCRATCH_MAX / ((int64_t)nmax * (nmax + 1));
+    if (fit < wg) wg = fit > 0 ? (int)fit : 1;
+  }
+  return wg;
+}
 
 // scratch doubles of a launch with list capacity `cap`: one nmax x (nmax + 1) system per
 // workgroup (64 x 1025 x 1026 doubles = 540 MB at nmax = 1025 only when >= 64 systems can
 // fail; a launch of few cells sizes it by its own capacity)
 extern "C" int64_t pfml_ridge_repair_work_doubles_cap(int nmax, int cap) {
-  return (int64_t)repair_wgs(cap) * nmax * (nmax + 1);
+  return (int64_t)repair_wgs(cap, nmax) * nmax * (nmax + 1);
 }
 
 extern "C" int64_t pfml_ridge_repair_work_doubles(int nmax) {
-  return (int64_t)REPAIR_WG * nmax * (nmax + 1);
+  return (int64_t)repair_wgs(REPAIR_WG, nmax) * nmax * (nmax + 1);
 }
 
 // list: cap ints, count: 1 int (zeroed by the caller, on the stream), work: see above.
@@ -164,7 +176,7 @@ extern "C" hipError_t pfml_ridge_repair(const double* SD, int64_t ldS, const dou
   const int tot = ncells * L;
   hipLaunchKernelGGL(ridge_flag_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, cd, ncells, L,
                      beta, ldo, list, count, cap);
-  hipLaunchKernelGGL(ridge_lu_repair_kernel, dim3(repair_wgs(cap)), dim3(RT), 0, st, SD, ldS, Sr, cd,
+  hipLaunchKernelGGL(ridge_lu_repair_kernel, dim3(repair_wgs(cap, nmax)), dim3(RT), 0, st, SD, ldS, Sr, cd,
                      lvec, L, beta, ldo, list, count, cap, work, nmax);
   return hipGetLastError();
 }

@@ -372,6 +372,11 @@ def ridge_plan(P: int, L: int, cell_src, cell_n, cell_scale, ncu: int = 256) -> 
         raise RuntimeError("CellDesc layout mismatch between python and libpfml_hip")
     nc = len(cell_src)
     cell_n = np.asarray(cell_n)
+    nlim = int(lib.pfml_ridge_nmax())
+    if nc and int(cell_n.max()) > nlim:
+        raise ValueError(f"ridge_plan: p = {int(cell_n.max()) - 1} is above the device ridge "
+                         f"grid's limit of n = p + 1 <= {nlim} (p <= {nlim - 1}); the CPU path "
+                         "has no limit")
     wsz = _work_doubles(cell_n, L)
     desc = np.zeros(nc, dtype=CELL_DTYPE)
     desc["src"] = np.asarray(cell_src, np.int64) * P * P
@@ -447,7 +452,9 @@ def _n_host_ptr(plan: dict):
 def band_path(plan: dict) -> bool:
     """True when the launch takes the band path (ridge_band.hip, n <= 528), whose non-SPD
     lambdas are repaired in the band domain inside the launch; the tridiagonal path
-    (ridge.hip, 528 < n <= 1024) leaves NaN markers for ``repair_launch``."""
+    (ridge.hip, 528 < n <= 2049, i.e. p up to 2048) leaves NaN markers for ``repair_launch``.
+    The launch's largest n decides for all its cells: ``ridge_groups`` keeps the production
+    entry from mixing the two kinds in one launch."""
     return plan["nmax"] <= nat.hip_lib().pfml_ridge_band_nmax()
 
 
@@ -468,6 +475,10 @@ def ridge_launch(plan: dict, d_desc: torch.Tensor, SD: torch.Tensor, Sr: torch.T
         lst = torch.empty(plan["nc"] * L, dtype=torch.int32, device=SD.device)
     if band and d_wgmap is None:
         raise ValueError("ridge_launch: the cooperative reduction needs the device wgmap")
+    if not band:
+        # PFML_RIDGE_BT_WY=0: cells with n > 1024 on the generic back-transform (the A/B arm of
+        # tools/bench_large_p.py) instead of the blocked MFMA kernel
+        nat.hip_lib().pfml_ridge_set_bt_wy(int(os.environ.get("PFML_RIDGE_BT_WY", "1") != "0"))
     sync = (torch.empty(plan["nc"] * COOP_SYNC_WORDS, dtype=torch.int32, device=SD.device)
             if band else None)
     if band:
@@ -537,12 +548,14 @@ def ridge_grid(SD: torch.Tensor, Sr: torch.Tensor, cell_src: np.ndarray, cell_n:
     S, P, _ = SD.shape
     L = int(lvec.numel())
     nc = len(cell_src)
+    # (the plan first: a cell above the device limit is refused before anything is queued)
+    plan = (ridge_plan(P, L, cell_src, cell_n, cell_scale, ncu=num_cus(SD.device))
+            if nc and nat.is_device(SD) else None)
     beta = torch.zeros((nc, L, P), dtype=SD.dtype, device=SD.device)
     if nc == 0:
         return beta
     if nat.is_device(SD):
         reset_coop_sync()
-        plan = ridge_plan(P, L, cell_src, cell_n, cell_scale, ncu=num_cus(SD.device))
         d_desc, d_wg = upload([plan["desc"], plan["wgmap"]], SD.device)
         lv = lvec.to(device=SD.device, dtype=torch.float64).contiguous()
         SDc, Src = SD.contiguous(), Sr.contiguous()
@@ -610,6 +623,26 @@ def two_streams() -> bool:
 
 _UTIL_PLANS: dict = {}
 
+BAND_NMAX = 528         # csrc/ridge_band.hip BNMAX (pfml_ridge_band_nmax): the band path's largest n
+
+
+def ridge_groups(cell_n, band_nmax: int = BAND_NMAX) -> list:
+    """Launch groups of ``ridge_utilities`` as index arrays into ``cell_n`` (pure host code, no
+    native call): the largest-n cells first, then the rest.  A launch's path is picked by its
+    largest n (``band_path``), so when the rest holds both tridiagonal-path cells
+    (n > ``band_nmax``) and band-path cells it is split in two, the band cells last: a band
+    cell is never solved on the tridiagonal path.  With at most one n above ``band_nmax`` these
+    are the two groups "largest" and "rest"."""
+    n = np.asarray(cell_n)
+    big = n == n.max()
+    rest_tri = ~big & (n > band_nmax)
+    rest_band = ~big & (n <= band_nmax)
+    if rest_tri.any() and rest_band.any():
+        parts = (big, rest_tri, rest_band)
+    else:
+        parts = (big, ~big)
+    return [np.nonzero(m)[0] for m in parts]
+
 
 def _utilities_plan(P: int, L: int, dev, cell_src, cell_n, cell_scale, job_cell, job_month,
                     job_n, split: bool = True) -> dict:
@@ -624,16 +657,19 @@ def _utilities_plan(P: int, L: int, dev, cell_src, cell_n, cell_scale, job_cell,
     hit = _UTIL_PLANS.get(key)
     if hit is not None:
         return hit
-    big = cell_n == cell_n.max()
     if split:
         # the largest cells (their own cooperative launch: the chip's CUs shared among them)
-        # and the rest (one workgroup each), each group on a stream of its own
-        parts = (big, ~big)
+        # and the rest (one workgroup each; band and tridiagonal cells apart), each group on a
+        # stream of its own
+        if nat.hip_lib().pfml_ridge_band_nmax() != BAND_NMAX:
+            raise RuntimeError("BAND_NMAX differs from libpfml_hip's band limit")
+        parts = ridge_groups(cell_n)
     else:
-        parts = (np.ones(len(cell_n), dtype=bool),)
+        parts = [np.arange(len(cell_n))]
     groups, arrays = [], []
-    for grp in parts:
-        cells = np.nonzero(grp)[0]
+    for cells in parts:
+        grp = np.zeros(len(cell_n), dtype=bool)
+        grp[cells] = True
         jobs = np.nonzero(grp[job_cell])[0]
         rp = ridge_plan(P, L, cell_src[cells], cell_n[cells], cell_scale[cells], ncu=num_cus(dev))
         # ridge_plan orders cells big-first and numbers outputs 0..: map to global rows
@@ -676,7 +712,8 @@ def ridge_utilities(SD: torch.Tensor, Sr: torch.Tensor, cell_src, cell_n, cell_s
                     job_n) -> tuple[torch.Tensor, torch.Tensor]:
     """(beta, obj) = (ridge_grid(...), quadform_utilities(D, R, beta, jobs)).
 
-    On a device the cells split into the largest-n group and the rest; each group's ridge ->
+    On a device the cells split into the largest-n group and the rest (``ridge_groups``: the
+    rest in two groups when it mixes band and tridiagonal cells); each group's ridge ->
     utilities chain is issued on its own HIP stream, the big group first, so the small cells'
     chain runs on the CUs the big cells' reduction leaves idle.  (Holding the small cells'
     utilities back until the big cells' solves are done measured slower: 5.43 vs 5.12 ms, the
