@@ -5,6 +5,11 @@ generation and the headline benchmark.
     python -m pfml main         --data-dir Data [--device cuda] [--checkpoint] [--check]
     python -m pfml prepare-data | estimate-cov | pfml-input | pfml-search-coef | pfml-hp-reals
                    | pfml-aim | pfml-hps | pfml-best-hps | get-additional-data | sp500-subset
+    python -m pfml pfml-ef      --data-dir Data --device cuda [--checkpoint]
+                   [--set ef.wealth=[1e9,1e11] --set ef.gamma_rel=[5,20]]
+                   (the wealth x gamma efficient frontier -> ef.csv, ef_pf.csv,
+                   plots/efficient_frontier.png; needs the prepare-data and estimate-cov
+                   outputs only; one process; not part of `main`)
     python -m pfml stages a,b,c  (several stages in one process)
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m pfml main ...   (RCCL, one rank/GPU)
 
@@ -48,7 +53,8 @@ def main(argv=None) -> int:
     ap.add_argument("--device", default=None, help="auto | cpu | cuda")
     ap.add_argument("--set", action="append", help="dotted override key=value")
     ap.add_argument("--config", default=None, help="YAML overrides (safe_load)")
-    ap.add_argument("--checkpoint", action="store_true", help="write artifacts + resume")
+    ap.add_argument("--checkpoint", action="store_true",
+                    help="write artifacts + resume (pfml-ef: resume at the first missing point)")
     ap.add_argument("--corrected", action="store_true", help="disable reference quirks Q1-Q3")
     ap.add_argument("--profile", action="store_true", help="roctx ranges + plots")
     ap.add_argument("--check", action="store_true",

@@ -20,6 +20,10 @@ CSV_COLUMNS = {
     "pf.csv": ["inv", "shorting", "turnover", "r", "tc", "eom_ret"],
     "pf_summary.csv": ["type", "n", "inv", "shorting", "turnover_notional", "r", "sd",
                        "sr_gross", "tc", "r_tc", "sr", "obj"],
+    "ef.csv": ["wealth_end", "gamma_rel", "type", "n", "inv", "shorting", "turnover_notional",
+               "r", "sd", "sr_gross", "tc", "r_tc", "sr", "obj", "s4_repairs", "s4_fallbacks",
+               "grid_recomputed_cells", "seconds"],
+    "ef_pf.csv": ["wealth_end", "gamma_rel", "inv", "shorting", "turnover", "r", "tc", "eom_ret"],
 }
 
 

@@ -9,6 +9,9 @@
                          chain as device GEMVs (no per-month host round trip), one N-vector
                          hand-off between ranks;
 * ``pf_ts`` / ``pf_summary`` - :220-259, :326-358 (quirks Q3, Q18);
+* ``backtest_layout`` / ``select_hps`` / ``backtest_device`` - the same selection, aims,
+                         recursion and statistics from the grid search's tensors with no
+                         DataFrame in between (one frontier point, models/frontier.py);
 * ``plots``            - cumulative-performance / hyper-parameter figures (matplotlib).
 """
 from __future__ import annotations
@@ -38,6 +41,10 @@ AIM_JOB = np.dtype([("s", "<u8"), ("ld", "<i8"), ("off", "<i8"), ("nrow", "<i4")
                     ("nk", "<i4")])
 
 log = get_logger("portfolio")
+
+
+class NoRankedHyperParameters(KeyError):
+    """A year whose December validation row has no ranked (p, l): every utility is NaN."""
 
 
 def _opt_hps(validation: pd.DataFrame, g: int) -> pd.DataFrame:
@@ -199,12 +206,12 @@ def _month_values(frame: pd.DataFrame, col: str, months: np.ndarray) -> np.ndarr
     return frame[col].to_numpy(np.float64)[o][_exact_lookup(mi[o], np.asarray(months), col)]
 
 
-def _weights_plan(cfg: Config, chars: pd.DataFrame, wealth: pd.DataFrame, aims: pd.DataFrame,
-                  oos_months: np.ndarray) -> dict:
-    """Host layout of the recursion, vectorised (no per-month Python loop): the valid rows of
-    every OOS month in id order (only the columns the recursion reads), each month's aim
-    weights aligned to them, the drift map from month t's rows to month t+1's (position of
-    each id of t+1 among t's rows, or -1 for a new name), and the month of every row."""
+def _rows_plan(chars: pd.DataFrame, oos_months: np.ndarray,
+               cols: tuple = ("id", "me", "tr_ld1", "lambda")) -> dict:
+    """The part of the recursion's host layout that depends on the panel alone: the valid rows
+    of every OOS month in id order (only the columns ``cols``), the drift map from month t's
+    rows to month t+1's (position of each id of t+1 among t's rows, or -1 for a new name), and
+    the month of every row."""
     mi_all = month_index(chars["eom"])
     months = np.asarray(oos_months, np.int64)
     # OOS membership by a month lookup table (months are a short integer range)
@@ -222,7 +229,7 @@ def _weights_plan(cfg: Config, chars: pd.DataFrame, wealth: pd.DataFrame, aims: 
     skey = mi_all[rows] * 10_000_000 + ids_sel
     if len(skey) > 1 and not (skey[1:] >= skey[:-1]).all():
         rows = rows[np.argsort(skey, kind="stable")]
-    cols = [c for c in ("id", "me", "tr_ld1", "lambda") if c in chars.columns]
+    cols = [c for c in cols if c in chars.columns]
     data = pd.DataFrame({c: chars[c].to_numpy()[rows] for c in cols})
     data["mi"] = mi_all[rows]
     mi = data["mi"].to_numpy()
@@ -230,15 +237,6 @@ def _weights_plan(cfg: Config, chars: pd.DataFrame, wealth: pd.DataFrame, aims: 
     stops = np.searchsorted(mi, months, "right")
     ids_all = data["id"].to_numpy(np.int64)
     trow = np.searchsorted(months, mi)                  # month position of every row
-    aim_key = month_index(aims["eom"]) * 10_000_000 + aims["id"].to_numpy(np.int64)
-    ak, av = aim_key, aims["w_aim"].to_numpy(np.float64)
-    if len(ak) > 1 and not (ak[1:] >= ak[:-1]).all():     # sort only if not already sorted
-        order = np.argsort(aim_key, kind="stable")
-        ak, av = ak[order], av[order]
-    key = mi * 10_000_000 + ids_all
-    p = np.clip(np.searchsorted(ak, key), 0, max(len(ak) - 1, 0))
-    w_aim = np.where((len(ak) > 0) & (ak[p] == key), av[p], np.nan) if len(ak) else \
-        np.full(len(key), np.nan)
     # row r of month t+1 -> row of the same id in month t (keys (t, id) are sorted)
     tk = trow * 10_000_000 + ids_all
     nxt = np.full(len(data), -1, np.int64)
@@ -249,7 +247,26 @@ def _weights_plan(cfg: Config, chars: pd.DataFrame, wealth: pd.DataFrame, aims: 
         hit = tk[q] == qk
         nxt[later] = np.where(hit, q - starts[trow[later] - 1], -1)
     return dict(data=data, months=months, starts=starts, stops=stops, ids=ids_all,
-                w_aim=w_aim, nxt=nxt, trow=trow, mu=_month_values(wealth, "mu_ld1", months))
+                nxt=nxt, trow=trow)
+
+
+def _weights_plan(cfg: Config, chars: pd.DataFrame, wealth: pd.DataFrame, aims: pd.DataFrame,
+                  oos_months: np.ndarray) -> dict:
+    """Host layout of the recursion, vectorised (no per-month Python loop): ``_rows_plan``
+    plus each month's aim weights aligned to its rows and the months' mu_ld1."""
+    pl = _rows_plan(chars, oos_months)
+    mi, ids_all = pl["data"]["mi"].to_numpy(), pl["ids"]
+    aim_key = month_index(aims["eom"]) * 10_000_000 + aims["id"].to_numpy(np.int64)
+    ak, av = aim_key, aims["w_aim"].to_numpy(np.float64)
+    if len(ak) > 1 and not (ak[1:] >= ak[:-1]).all():     # sort only if not already sorted
+        order = np.argsort(aim_key, kind="stable")
+        ak, av = ak[order], av[order]
+    key = mi * 10_000_000 + ids_all
+    p = np.clip(np.searchsorted(ak, key), 0, max(len(ak) - 1, 0))
+    w_aim = np.where((len(ak) > 0) & (ak[p] == key), av[p], np.nan) if len(ak) else \
+        np.full(len(key), np.nan)
+    pl.update(w_aim=w_aim, mu=_month_values(wealth, "mu_ld1", pl["months"]))
+    return pl
 
 
 def _same_device(a: torch.device, b) -> bool:
@@ -279,6 +296,37 @@ def m_cache_positions(m_cache: dict | None, months: np.ndarray, ns: np.ndarray, 
                                for p, i in zip(p_, ids)):
         return None
     return torch.as_tensor(p_, device=m_cache["mt"].device)
+
+
+def _chain(mt_all: torch.Tensor, a_all: torch.Tensor, wa: torch.Tensor, grow: torch.Tensor,
+           nmap_t: torch.Tensor, hit_t: torch.Tensor, ws0: torch.Tensor):
+    """The sequential recursion over the Bm months of mt_all [Bm, N, N] (padded [Bm, N]
+    operands, w_start of the first month ws0 [N]): (Wst, Wopt, w_start after the last)."""
+    Bm, N = wa.shape
+    f64 = dict(dtype=torch.float64, device=wa.device)
+    Wst = torch.zeros((Bm, N), **f64)
+    Wopt = torch.zeros((Bm, N), **f64)
+    ws = ws0
+    if nat.is_device(mt_all) and N <= int(nat.hip_lib().pfml_weights_chain_max_n()):
+        # one persistent-workgroup launch for the whole chain (csrc/weights.hip)
+        ws = torch.empty(N, **f64)
+        if Bm:
+            nat.check(nat.hip_lib().pfml_weights_chain(
+                mt_all.data_ptr(), mt_all.stride(1), mt_all.stride(0), a_all.data_ptr(),
+                wa.data_ptr(),
+                grow.contiguous().data_ptr(), nmap_t.data_ptr(), hit_t.data_ptr(), N,
+                ws0.contiguous().data_ptr(), Bm, N, Wst.data_ptr(), Wopt.data_ptr(),
+                ws.data_ptr(), nat.stream_of(mt_all)), "pfml_weights_chain")
+        else:
+            ws.copy_(ws0)
+    else:
+        for i in range(Bm):
+            Wst[i] = ws
+            d = (ws - wa[i]) / a_all[i]
+            wopt = wa[i] + a_all[i] * torch.mv(mt_all[i], d)
+            Wopt[i] = wopt
+            ws = (wopt * grow[i])[nmap_t[i]] * hit_t[i]             # next month's w_start
+    return Wst, Wopt, ws
 
 
 def pfml_weights(cfg: Config, chars: pd.DataFrame, barra: BarraCov, wealth: pd.DataFrame,
@@ -407,28 +455,7 @@ def pfml_weights(cfg: Config, chars: pd.DataFrame, barra: BarraCov, wealth: pd.D
         me = data["me"].to_numpy(np.float64)[g0]
         ws0 = torch.zeros(N, **f64)
         ws0[: len(g0)] = torch.as_tensor(me / me.sum(), **f64)    # value-weighted start
-    Wst = torch.zeros((Bm, N), **f64)
-    Wopt = torch.zeros((Bm, N), **f64)
-    ws = ws0
-    if nat.is_device(mt_all) and N <= int(nat.hip_lib().pfml_weights_chain_max_n()):
-        # one persistent-workgroup launch for the whole chain (csrc/weights.hip)
-        ws = torch.empty(N, **f64)
-        if Bm:
-            nat.check(nat.hip_lib().pfml_weights_chain(
-                mt_all.data_ptr(), mt_all.stride(1), mt_all.stride(0), a_all.data_ptr(),
-                wa.data_ptr(),
-                grow.contiguous().data_ptr(), nmap_t.data_ptr(), hit_t.data_ptr(), N,
-                ws0.contiguous().data_ptr(), Bm, N, Wst.data_ptr(), Wopt.data_ptr(),
-                ws.data_ptr(), nat.stream_of(mt_all)), "pfml_weights_chain")
-        else:
-            ws.copy_(ws0)
-    else:
-        for i in range(Bm):
-            Wst[i] = ws
-            d = (ws - wa[i]) / a_all[i]
-            wopt = wa[i] + a_all[i] * torch.mv(mt_all[i], d)
-            Wopt[i] = wopt
-            ws = (wopt * grow[i])[nmap_t[i]] * hit_t[i]             # next month's w_start
+    Wst, Wopt, ws = _chain(mt_all, a_all, wa, grow, nmap_t, hit_t, ws0)
     if env.is_dist:
         coll.send_next(ws)
     th("s9.chain")
@@ -447,6 +474,234 @@ def pfml_weights(cfg: Config, chars: pd.DataFrame, barra: BarraCov, wealth: pd.D
                         "mu_ld1": pl["mu"][trow],
                         "id": ids_all, "tr_ld1": tr1, "w_start": w_start, "w": w})
     th("s9.gather+frame")
+    return out
+
+
+def backtest_layout(cfg: Config, chars: pd.DataFrame, wealth: pd.DataFrame,
+                    oos_months: np.ndarray, signal_months: np.ndarray, signal_ids: list,
+                    device, n_pad: int = 0) -> dict:
+    """Everything of ``backtest_device`` that does not depend on the frontier point (the wealth
+    level, gamma, the chosen hyper-parameters): the valid rows of every OOS month, the drift
+    map, the position of every row's id among the month's S4 signal rows, and the padded
+    [B, N] device copies of ret_ld1, lambda, the drift factor (1 + tr_ld1) / (1 + mu_ld1) and
+    the value-weighted start.  ``wealth`` is read for mu_ld1 only (the same at every point).
+    Built once, reused for every point."""
+    dev = torch.device(device)
+    f64 = dict(dtype=torch.float64, device=dev)
+    pl = _rows_plan(chars, oos_months, cols=("id", "me", "tr_ld1", "lambda", "ret_ld1"))
+    data, months, starts, stops = pl["data"], pl["months"], pl["starts"], pl["stops"]
+    B = len(months)
+    ns = stops - starts
+    N = max(int(ns.max()) if B else 1, int(n_pad))
+    bi = np.repeat(np.arange(B), ns)
+    col = np.arange(int(ns.sum())) - np.repeat(starts, ns)
+    mu = _month_values(wealth, "mu_ld1", months)
+
+    def padded(vals: np.ndarray, fill: float, dtype=np.float64) -> np.ndarray:
+        out = np.full((B, N), fill, dtype)
+        out[bi, col] = vals
+        return out
+
+    # position of every row's id among its month's signal rows (-1: no aim for that name)
+    mpos = {int(m): i for i, m in enumerate(np.asarray(signal_months))}
+    missing = [int(d) for d in months if int(d) not in mpos]
+    if missing:
+        raise KeyError(f"no S4 signals for OOS month(s) {missing[:3]}")
+    sig_pos = np.asarray([mpos[int(d)] for d in months], np.int64)
+    smap = np.full(len(data), -1, np.int64)
+    identity = True
+    for t in range(B):
+        sid = np.asarray(signal_ids[sig_pos[t]], np.int64)
+        mine = pl["ids"][starts[t]:stops[t]]
+        if len(sid) == len(mine) and np.array_equal(sid, mine):
+            smap[starts[t]:stops[t]] = np.arange(len(mine))
+            continue
+        identity = False
+        o = np.argsort(sid, kind="stable")
+        p = np.clip(np.searchsorted(sid[o], mine), 0, max(len(sid) - 1, 0))
+        if len(sid):
+            smap[starts[t]:stops[t]] = np.where(sid[o][p] == mine, o[p], -1)
+    nmap = np.zeros((B, N), np.int64)
+    hit = np.zeros((B, N))
+    if B > 1:
+        later = pl["trow"] >= 1
+        q = pl["nxt"][later]
+        nmap[bi[later] - 1, col[later]] = np.maximum(q, 0)
+        hit[bi[later] - 1, col[later]] = q >= 0
+    ws0 = np.zeros(N)
+    if B:
+        me = data["me"].to_numpy(np.float64)[starts[0]:stops[0]]
+        ws0[: len(me)] = me / me.sum()                    # value-weighted start
+    tr1 = data["tr_ld1"].to_numpy(np.float64)
+    grow = padded(1.0 + tr1, 1.0) / (1.0 + mu)[:, None]
+    return dict(
+        plan=pl, months=months, ns=ns, N=N, B=B, mu=mu, sig_pos=sig_pos, sig_identity=identity,
+        ids=[pl["ids"][starts[t]:stops[t]] for t in range(B)],
+        live=torch.as_tensor(padded(np.ones(len(data), bool), False, bool), device=dev),
+        smap=torch.as_tensor(padded(smap, -1, np.int64), device=dev),
+        ret=torch.as_tensor(padded(data["ret_ld1"].to_numpy(np.float64), 0.0), **f64),
+        lam=torch.as_tensor(padded(data["lambda"].to_numpy(np.float64), 0.0), **f64),
+        grow=torch.as_tensor(grow, **f64), nmap=torch.as_tensor(nmap, device=dev),
+        hit=torch.as_tensor(hit, **f64), ws0=torch.as_tensor(ws0, **f64),
+        n_rows=torch.as_tensor(ns, dtype=torch.int32, device=dev))
+
+
+def select_hps(grid, cfg: Config) -> dict:
+    """{hp year: (g, p, l)} from the score tensors, with no validation frame: per g the
+    December dense-rank-1 (p, l) of the year (``_opt_hps`` / ``aim_portfolios``: the LAST
+    rank-1 row in the frame's (p, l, g') order, quirk Q2's extra rows of g' <= g included in
+    compat mode), then across g the first maximum of cum_obj in the order of the concatenated
+    frames (``best_hps``: rank(method="first") over g, p, l, g').  The (p, l) returned for a
+    year are those of the chosen g's aim portfolio.  Only the December slice of cum_obj and
+    rank is copied to the host."""
+    from . import search
+    order = np.argsort(grid.val_months, kind="stable")
+    vm = np.asarray(grid.val_months)[order]
+    er = month_end(vm + 1)
+    dec = np.nonzero(er.month.to_numpy() == 12)[0]
+    years = er.year.to_numpy()[dec]
+    if len(np.unique(years)) != len(years):
+        raise ValueError("select_hps: more than one December validation month in a year")
+    obj = grid.obj[torch.as_tensor(order, device=grid.obj.device)]
+    di = torch.as_tensor(dec, device=obj.device)
+    nP, L = len(grid.p_vec), len(grid.l_vec)
+    cums, ranks, ks = [], [], []
+    for _, cum, rank in search.validation_scores_all(obj, cfg.run.compat_mode):
+        ks.append(cum.shape[1])
+        # rows in the frame's order (p, l, g') for every December
+        cums.append(cum.index_select(0, di).permute(0, 2, 3, 1).reshape(len(dec), -1))
+        ranks.append(rank.index_select(0, di).permute(0, 2, 3, 1).reshape(len(dec), -1))
+    cum_h = torch.cat(cums, 1).cpu().numpy()
+    rank_h = torch.cat(ranks, 1).cpu().numpy()
+    offs = np.concatenate([[0], np.cumsum([k * nP * L for k in ks])])
+    out = {}
+    for yi, y in enumerate(years):
+        row = cum_h[yi]
+        if np.isnan(row).all():
+            continue                                   # no ranked row: the year has no choice
+        g = int(np.searchsorted(offs, int(np.nanargmax(row)), "right") - 1)
+        r1 = np.nonzero(rank_h[yi, offs[g]:offs[g + 1]] == 1)[0]
+        if len(r1) == 0:
+            continue
+        pi, li = np.unravel_index(int(r1[-1]), (nP, L, ks[g]))[:2]
+        out[int(y)] = (g, int(grid.p_vec[pi]), int(li))
+    return out
+
+
+def backtest_device(cfg: Config, grid, inputs, layout: dict, wealth: pd.DataFrame, device,
+                    keep_weights: bool = False, clock=None) -> dict:
+    """S6 selection -> S7 aims -> S9 recursion -> per-month statistics with no DataFrame in
+    between (the stage functions ``validation_frame`` / ``aim_portfolios`` / ``best_hps`` /
+    ``pfml_weights`` / ``pf_ts`` compute the same numbers through frames).
+
+    ``grid``: the gathered GridResult of this point (all hp years local: one process);
+    ``inputs``: its PfmlInputs with ``m_keep`` for the OOS months (S4's m_tilde and a);
+    ``layout``: ``backtest_layout``; ``wealth``: the point's wealth path.  Returns
+    {"stats": [B, 5] ndarray (inv, shorting, turnover, r, tc), "months", "pf": the pf.csv
+    frame, "chosen": {hp year: (g, p, l)} for the years the OOS months draw on, "recomputed": the CPU chain re-run happened,
+    "weights": the weights.csv frame if ``keep_weights``}.  ``clock(name)`` is called after
+    each phase (selection, aims, chain, stats) by the measurement tool."""
+    from ..ops.pfstats import STAT_COLUMNS, pf_stats
+    tick = clock or (lambda name: None)
+    dev = torch.device(device)
+    f64 = dict(dtype=torch.float64, device=dev)
+    months, ns, N, B = layout["months"], layout["ns"], layout["N"], layout["B"]
+    picks = select_hps(grid, cfg)
+    tick("selection")
+
+    # ---- aims of the chosen (g, month) jobs only, into the chain's padded layout -------
+    byear = np.asarray(grid.years_local)
+    meta = []                                      # (g, signal position, p, l, year idx, p idx)
+    chosen: dict = {}                              # the hp years the OOS months draw on
+    for t, d in enumerate(months):
+        oos_year = int(month_end(int(d) + 1).year[0])
+        if oos_year - 1 not in picks:
+            raise NoRankedHyperParameters(
+                f"no December rank-1 hyper-parameters for {oos_year - 1}")
+        g, p, l = chosen[oos_year - 1] = picks[oos_year - 1]
+        hit = np.nonzero(byear == oos_year)[0]             # quirk Q13
+        if len(hit) == 0:
+            raise KeyError(f"coefficients of hp year {oos_year} are not on this rank")
+        meta.append((g, int(layout["sig_pos"][t]), p, l, int(hit[0]), cfg.p_vec.index(p)))
+    beta = grid.beta
+    idx = [torch.as_tensor([m[k] for m in meta], device=beta.device) for k in (0, 4, 5, 3)]
+    coefs = beta[idx[0], idx[1], idx[2], idx[3]].contiguous().to(dev)    # [B, P]
+    sig = [inputs.signal_t[m[0]][m[1]] for m in meta]
+    nsig = np.asarray([int(x.shape[0]) for x in sig], np.int64)
+    direct = layout["sig_identity"]
+    Na = N if direct else max(int(nsig.max()) if B else 1, 1)
+    wa = torch.zeros((B, Na), **f64)
+    if B and dev.type == "cuda" and all(x.is_cuda and x.stride(-1) == 1 for x in sig):
+        from ..ops.ridge import upload
+        if nat.hip_lib().pfml_aim_job_size() != AIM_JOB.itemsize:
+            raise RuntimeError("AimJob layout mismatch between python and libpfml_hip")
+        jobs = np.zeros(B, AIM_JOB)
+        jobs["s"] = [x.data_ptr() for x in sig]
+        jobs["ld"] = [x.stride(0) for x in sig]
+        jobs["off"] = np.arange(B, dtype=np.int64) * Na
+        jobs["nrow"] = nsig
+        jobs["nk"] = [m[2] + 1 for m in meta]
+        (dj,) = upload([jobs], dev)
+        nat.check(nat.hip_lib().pfml_aim_gemv(dj.data_ptr(), B, int(nsig.max()),
+                                              coefs.data_ptr(), coefs.shape[1], wa.data_ptr(),
+                                              nat.stream_of(wa)), "pfml_aim_gemv")
+    else:
+        for t, (s_, m) in enumerate(zip(sig, meta)):
+            wa[t, : s_.shape[0]] = (s_[:, : m[2] + 1] @ coefs[t, : m[2] + 1].to(s_.device)).to(dev)
+    if not direct:                                 # signal rows -> the month's valid rows
+        sm = layout["smap"]
+        wa = torch.where(sm >= 0, wa.gather(1, sm.clamp(min=0)),
+                         torch.full((), float("nan"), **f64))
+        wa = torch.where(layout["live"], wa, torch.zeros((), **f64))
+
+    tick("aims")
+
+    # ---- m_t from S4, the chain, the statistics ----------------------------------------
+    kpos = m_cache_positions(inputs.m_keep, months, ns, layout["ids"], N, dev)
+    if kpos is None:
+        raise RuntimeError("backtest_device needs S4's m_tilde of every OOS month "
+                           "(build_inputs(..., keep_m=oos months), fp64, same device)")
+    mk = inputs.m_keep
+    if len(kpos) == mk["mt"].shape[0] and bool((kpos == torch.arange(len(kpos),
+                                                                     device=kpos.device)).all()):
+        mt_all, a_all = mk["mt"][:, :N, :N], mk["a"][:, :N].contiguous()
+    else:
+        mt_all = mk["mt"].index_select(0, kpos)[:, :N, :N]
+        a_all = mk["a"].index_select(0, kpos)[:, :N].contiguous()
+    args = (wa, layout["grow"], layout["nmap"], layout["hit"], layout["ws0"])
+    Wst, Wopt, _ = _chain(mt_all, a_all, *args)
+    # failure detection as in the pfml-best-hps stage: a non-finite w_start means a fault in
+    # the device chain -> the recursion is recomputed on the CPU
+    recomputed = False
+    live = layout["live"]
+    if cfg.run.fault_inject.startswith("pfml-best-hps") and B:
+        Wst[B // 2, 0] = float("nan")
+    if not bool(torch.isfinite(torch.where(live, Wst, torch.zeros((), **f64))).all()):
+        log.warning("non-finite w_start: weight recursion recomputed on the CPU")
+        Wst, Wopt, _ = (x.to(dev) for x in _chain(mt_all.cpu(), a_all.cpu(),
+                                                  *(x.cpu() for x in args)))
+        recomputed = True
+        if not bool(torch.isfinite(torch.where(live, Wst, torch.zeros((), **f64))).all()):
+            raise FloatingPointError("w_start stays non-finite on the CPU recursion")
+    # rows with a missing aim stay NaN like the reference's merge would leave them
+    Wopt = torch.where(torch.isnan(wa), wa, Wopt)
+    tick("chain")
+    wvals = torch.as_tensor(_month_values(wealth, "wealth", months), **f64)
+    stats = pf_stats(Wopt, Wst, layout["ret"], layout["lam"], layout["n_rows"], wvals)
+    stats_h = stats.cpu().numpy()
+    tick("stats")
+    eom = month_end(months)
+    pf = pd.DataFrame(stats_h, columns=list(STAT_COLUMNS))
+    # quirk Q3 (pf_ts): eom_ret == eom in compat mode
+    pf["eom_ret"] = eom if cfg.run.compat_mode else eom + pd.offsets.MonthEnd(1)
+    out = {"stats": stats_h, "months": months, "pf": pf, "chosen": chosen,
+           "recomputed": recomputed}
+    if keep_weights:
+        pl = layout["plan"]
+        out["weights"] = pd.DataFrame({
+            "eom": month_end(pl["data"]["mi"].to_numpy()), "mu_ld1": layout["mu"][pl["trow"]],
+            "id": pl["ids"], "tr_ld1": pl["data"]["tr_ld1"].to_numpy(np.float64),
+            "w_start": Wst[live].cpu().numpy(), "w": Wopt[live].cpu().numpy()})
     return out
 
 

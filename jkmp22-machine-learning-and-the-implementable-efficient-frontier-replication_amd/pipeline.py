@@ -13,6 +13,7 @@ Stages (CLI names) and the reference script each one replaces:
     pfml-aim             PFML_aim_fun.py
     pfml-hps             PFML_hps.py
     pfml-best-hps        PFML_best_hps.py
+    pfml-ef              (none: the wealth x gamma frontier of settings["ef"]; not in ``main``)
 
 State flows in memory within one process; with ``checkpoint=True`` every stage also writes
 its artifact + done-marker (utils/artifacts.py) so a later run resumes from the first stage
@@ -58,7 +59,7 @@ log = get_logger("pipeline")
 
 MAIN_STAGES = ["prepare-data", "estimate-cov", "pfml-input", "pfml-search-coef",
                "pfml-hp-reals", "pfml-aim", "pfml-hps", "pfml-best-hps"]
-ALL_STAGES = ["get-additional-data", "sp500-subset"] + MAIN_STAGES
+ALL_STAGES = ["get-additional-data", "sp500-subset"] + MAIN_STAGES + ["pfml-ef"]
 
 # settings sections (and run options) each stage's output depends on (for resume keys);
 # keys chain, so a change invalidates the stage and everything downstream
@@ -73,6 +74,9 @@ _DEPS = {
     "pfml-aim": ("pf",),
     "pfml-hps": (),
     "pfml-best-hps": ("compat_mode", "iterations"),
+    # the frontier re-runs S4-S9 per point from the prepare-data / estimate-cov outputs
+    "pfml-ef": ("ef", "pf_ml", "Transaction_Costs", "seed_no", "compat_mode", "precision",
+                "iterations", "pf", "mu", "lb_hor"),
 }
 # stages whose artifacts are per rank (resume per shard)
 _SHARDED = ("pfml-input", "pfml-search-coef")
@@ -450,3 +454,26 @@ class Pipeline:
             portfolio.plots(pf, best, float(self.cfg.pf_set["gamma_rel"]),
                             os.path.join(d, "plots"))
         log.info("pf_summary:\n" + summ.to_string(index=False))
+
+    def _pfml_ef(self):
+        """The efficient frontier (models/frontier.py): Portfolio-ML at every point of
+        settings["ef"], from the prepare-data and estimate-cov outputs alone.  With
+        ``checkpoint`` the finished points are kept in an artifact and a resumed stage
+        continues at the first missing point."""
+        from .models import frontier
+        if self.env.world_size > 1:
+            raise RuntimeError(frontier.WORLD_ERROR)
+        self._load_common()
+        st = self.state
+        ck = self.store.path("pfml-ef", "points.json") if self.checkpoint else None
+        out = frontier.efficient_frontier(self.cfg, st["chars"], st["barra"], st["wealth"],
+                                          st["risk_free"], self.device, checkpoint=ck,
+                                          checkpoint_key=self._keys["pfml-ef"])
+        d = self.cfg.run.data_dir
+        io.write_csv(out["ef"], d, "ef.csv")
+        io.write_csv(out["pf"], d, "ef_pf.csv")
+        st.update(ef=out["ef"], ef_pf=out["pf"])
+        if self.cfg.run.plots:
+            frontier.plot_frontier(out["ef"], os.path.join(d, "plots"))
+        log.info("efficient frontier:\n" + out["ef"][["wealth_end", "gamma_rel", "r", "sd",
+                                                      "tc", "r_tc", "obj"]].to_string(index=False))
