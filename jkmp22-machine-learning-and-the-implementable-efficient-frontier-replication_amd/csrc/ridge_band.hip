@@ -532,9 +532,11 @@ __device__ __forceinline__ void coop_x_chunk(const double* __restrict__ A, int l
         a1[v][q] = x.y;
       }
     });
-    // (rows >= m of U are zero; the clamp keeps a last chunk inside Us)
-    b0[v] = Us[min(kk, BMP - 1)][c16];
-    b1[v] = Us[min(kk + 1, BMP - 1)][c16];
+    // (rows >= m of U are zero, and Us has BB zero rows behind row BMP - 1: a chunk that
+    // starts 16 mod 32 runs to k = BMP + 15 at m = BMP.  Clamped to row BMP - 1, a live row
+    // there, n = 528 gave wrong betas.)
+    b0[v] = Us[min(kk, BMP + BB - 1)][c16];
+    b1[v] = Us[min(kk + 1, BMP + BB - 1)][c16];
   }
 #pragma unroll
   for (int v = 0; v < NV; ++v)
@@ -611,14 +613,21 @@ constexpr UpdRows make_upd_rows() {
 }
 __constant__ UpdRows kUpdRows = make_upd_rows();
 
-template <bool TIMED>
+// SOLO: the instance of a launch whose every cell has K = 1 (pfml_ridge_band_launch: nwg ==
+// ncells).  K is a compile-time 1, so the hand-off code (published V / T / W / partials,
+// CoopSync polling) is gone, and since no other workgroup ever reads this cell's bytes the tile
+// stores, the hand-off words and z use plain accesses: a plain store keeps the line in the XCD's
+// L2 for the next panel's X phase and update, where a write-through (sc1) store drops it.  The
+// arithmetic is the general kernel's K = 1 path: the same bits.  The sync words are still
+// passed (zeroed by the launch): the back-transform reads the error word, which stays 0.
+template <bool TIMED, bool SOLO>
 __global__ __launch_bounds__(NTR) void band_coop_kernel(
     const double* __restrict__ SD, int64_t ldS, const double* __restrict__ Sr,
     const RidgeCellDesc* __restrict__ cells, int L, double* __restrict__ work,
     const int* __restrict__ wgmap, unsigned* __restrict__ syncw, long long* __restrict__ tim,
     unsigned spin_max) {
   __shared__ double Vs[BMP][LS];       // V_p (rows >= m zero); the QR WG: panel p+1, V_{p+1}
-  __shared__ double Ws[BMP][LS];       // U = V T, then W
+  __shared__ double Ws[BMP + BB][LS];  // U = V T, then W; BB rows of zeros behind (X phase)
   __shared__ double red[NWR][BB * BB]; // QR scratch, canonical sums, update transposes
   __shared__ double Ts[BB][LS];
   __shared__ double taus[BB];
@@ -626,7 +635,9 @@ __global__ __launch_bounds__(NTR) void band_coop_kernel(
   __shared__ int err_s;
 
   const int code = wgmap[blockIdx.x];
-  const int cell = code >> 8, w = (code >> 4) & 15, K = (code & 15) + 1;
+  const int cell = code >> 8;
+  const int w = SOLO ? 0 : (code >> 4) & 15, K = SOLO ? 1 : (code & 15) + 1;
+  constexpr int AUX = SOLO ? 0 : 16;             // sc1 (write-through) unless solo
   const RidgeCellDesc cd = cells[cell];
   const int n = cd.n;
   const int lda = band_npad(n), nb = lda / BB;
@@ -648,7 +659,7 @@ __global__ __launch_bounds__(NTR) void band_coop_kernel(
   auto st2 = [&](unsigned off, bool ok, double x, double y) {
     const double2 v = make_double2(x, y);
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsA,
-                                           ok ? off : abytes, 0, 16);
+                                           ok ? off : abytes, 0, AUX);
   };
   // the hand-off words (V, T, W, partials, z) through a descriptor on the cell's workspace:
   // write-through (sc1) 8-byte buffer stores and sc1 buffer loads (not atomics: a loop's loads
@@ -656,11 +667,11 @@ __global__ __launch_bounds__(NTR) void band_coop_kernel(
   const auto rsW = __builtin_amdgcn_make_buffer_rsrc(A, 0, 0x7ffffff0, 0x00020000);
   auto ldw = [&](const double* p) -> double {
     return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(
-                                          rsW, (unsigned)((p - A) * 8), 0, 16));
+                                          rsW, (unsigned)((p - A) * 8), 0, AUX));
   };
   auto stw = [&](double* p, double v) {
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), rsW,
-                                          (unsigned)((p - A) * 8), 0, 16);
+                                          (unsigned)((p - A) * 8), 0, AUX);
   };
   long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   long long tlast = 0;
@@ -671,6 +682,7 @@ __global__ __launch_bounds__(NTR) void band_coop_kernel(
     tlast = now;                                                         \
   }
   if (t_ == 0) err_s = 0;
+  for (int e = t_; e < BB * LS; e += NTR) (&Ws[BMP][0])[e] = 0.0;   // (visible after the sync below)
 
   // ---- A = S * scale (the lower block triangle incl. the diagonal blocks, zero padding),
   //      z = r * scale: row blocks gb = w (mod K)
@@ -1710,6 +1722,11 @@ extern "C" hipError_t pfml_band_qr_bench(const double* P, int m, int nblocks, in
   return hipGetLastError();
 }
 
+// 0: every launch takes the general cooperative kernel, also one whose cells all have K = 1
+// (PFML_COOP_SOLO=0, the A/B arm of the solo instance).
+static int g_coop_solo = 1;
+extern "C" void pfml_coop_set_solo(int on) { g_coop_solo = on ? 1 : 0; }
+
 // Poll bound of the cooperative reduction's hand-off waits for later launches (0: default).
 extern "C" void pfml_coop_set_spin_max(unsigned n) { g_coop_spin_max = n ? n : COOP_SPIN_MAX; }
 
@@ -1765,12 +1782,19 @@ extern "C" hipError_t pfml_ridge_band_launch(const double* SD, int64_t ldS, cons
     return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(syncw, 0, (size_t)ncells * COOP_SYNC * sizeof(unsigned), st);
   if (e != hipSuccess) return e;
-  if (tim != nullptr)
-    hipLaunchKernelGGL(band_coop_kernel<true>, dim3(nwg), dim3(NTR), 0, st, SD, ldS, Sr, cd, L,
-                       work, wgmap, syncw, tim, g_coop_spin_max);
-  else
-    hipLaunchKernelGGL(band_coop_kernel<false>, dim3(nwg), dim3(NTR), 0, st, SD, ldS, Sr, cd, L,
-                       work, wgmap, syncw, tim, g_coop_spin_max);
+  // nwg == ncells: every cell has K = 1, the solo instance (no hand-offs, plain stores)
+  const bool solo = g_coop_solo != 0 && nwg == ncells;
+#define COOP_LAUNCH(TIMED, SOLO)                                                            \
+  hipLaunchKernelGGL((band_coop_kernel<TIMED, SOLO>), dim3(nwg), dim3(NTR), 0, st, SD, ldS, Sr, \
+                     cd, L, work, wgmap, syncw, tim, g_coop_spin_max)
+  if (tim != nullptr) {
+    if (solo) COOP_LAUNCH(true, true);
+    else COOP_LAUNCH(true, false);
+  } else {
+    if (solo) COOP_LAUNCH(false, true);
+    else COOP_LAUNCH(false, false);
+  }
+#undef COOP_LAUNCH
   // (timing: the cooperative kernel fills 16 slots per cell, the solve's two go after them)
   hipLaunchKernelGGL(ridge_band_solve_kernel, dim3(ncells * ((L + 15) / 16)), dim3(NTS), 0, st,
                      cd, lvec, L, work,

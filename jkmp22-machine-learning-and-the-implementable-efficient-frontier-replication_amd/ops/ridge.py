@@ -483,6 +483,10 @@ def ridge_launch(plan: dict, d_desc: torch.Tensor, SD: torch.Tensor, Sr: torch.T
             if band else None)
     if band:
         _spin_from_env()
+        # PFML_COOP_SOLO=0: the general cooperative kernel also for a launch whose cells all
+        # have K = 1 (the A/B arm of the solo instance; absent from an older PFML_HIP_LIB build)
+        if hasattr(nat.hip_lib(), "pfml_coop_set_solo"):
+            nat.hip_lib().pfml_coop_set_solo(int(os.environ.get("PFML_COOP_SOLO", "1") != "0"))
         # every launch's sync words are kept until the next grid search starts (the big and the
         # small cells' launches run on two streams: neither may hide the other's timeouts)
         LAST_COOP_SYNC.append(sync)
