@@ -15,11 +15,15 @@
 // b_{n-1} (r_{n-1} - D_{n-1,n-1} b_{n-1} / 2) is added by the reduce kernel: 1 / 5 fewer
 // tile-steps at n = 65, 2 / 15 at 129, 5 / 45 at 257, 9 / 153 at 513.
 //
-// Tile: 64 rows of D x 112 lambda columns (L <= 112) x 1 (or 2) validation months of one cell
-// per 256-thread workgroup (3 per CU); each wave owns 16 rows x 7 MFMA 16x16 accumulators per
-// month.  Every workgroup writes a deterministic per-row-tile
-// partial; a second tiny kernel sums the partials in a fixed order (bitwise reproducible, no
-// float atomics).
+// Tile: 64 rows of D x 112 lambda columns (L <= 112) of one job per 256-thread workgroup (3
+// per CU); each wave owns 16 rows x 7 MFMA 16x16 accumulators.  Every workgroup writes a
+// deterministic per-row-tile partial; a second tiny kernel sums the partials in a fixed order
+// (bitwise reproducible, no float atomics).  The host lists the tiles longest-first
+// (tile_job[tile] = job << 5 | row tile, ops/ridge.py quad_plan).
+//
+// D_t is symmetric:  b'Db = sum_I b_I'(D_II b_I + 2 sum_{K>I} D_IK b_K).  A row tile I only
+// walks K >= I, with the diagonal block weighted 1/2, so  acc = U_I / 2  and half the flops
+// and D bytes of the full product are spent.
 //
 // Forms (ops/ridge.py quad_launch picks one per launch):
 //  * quadform_pipe_kernel (default): the direct-A form below with a software-pipelined K
@@ -29,10 +33,9 @@
 //    epilogue whose loads go out in one batch.  Tiles that are not aligned go to
 //    quadform_rest_kernel, the direct form's loop, in a second launch.
 //  * quadform_direct_kernel (PFML_QUAD_DIRECT=1): the direct-A form for every tile.
-//  * quadform_kernel<1|2> (PFML_QUAD_DIRECT=0, PFML_QUAD_MM=1|2): D and beta staged in LDS.
 // The pipelined and the direct form add the same products in the same order (the diagonal
 // block's weight 1/2 is a power of two wherever it is applied), so barring underflow they
-// agree bitwise (they do on the benchmark's grid); the LDS-staged forms have their own k order.
+// agree bitwise (they do on the benchmark's grid).
 #include "common.h"
 #include <cstdlib>
 #include <type_traits>
@@ -40,18 +43,10 @@
 namespace {
 
 constexpr int BK = 16, NCOL = 112, NTILE = NCOL / 16, BM = 64, NT = 256, NW = NT / 64;
-// Months per workgroup (the host's plan decides, ops/ridge.py quad_plan): 1 by default; 2
-// (PFML_QUAD_MM=2) lets the two validation months of one tile share the cell's beta, so every
-// beta K-tile staged in LDS feeds two D tiles (half the beta traffic, twice the MFMAs per
-// barrier) - measured slower on the headline step (5.90 vs 5.78 ms: 2 instead of 3 resident
-// workgroups per CU), kept for the A/B.
-// Earlier variants measured slower and removed: 128-row tiles (6.76 vs 6.64 ms per step) and
-// a prefetch distance of 2 (1.20 vs 1.33 ms), profiles/r02_quad_pf_ab.json.
-// Both operands are staged k-contiguous, as they sit in HBM ([row][k] for D, [lambda][k] for
-// beta), with a row stride of BK + 2 = 18 doubles: the coalesced global rows are stored
-// without bank conflicts, and a fragment read (16 rows x 2 k per 32-lane group) hits 32
-// distinct bank pairs.  (A [k][row] image made every staging store a 16-way conflict.)
-constexpr int KS = BK + 2;
+// Earlier variants measured slower and removed: 128-row tiles (6.76 vs 6.64 ms per step), a
+// prefetch distance of 2 (1.20 vs 1.33 ms), profiles/r02_quad_pf_ab.json, and the forms that
+// staged D as well as beta in LDS, one or two validation months per tile (superseded by the
+// direct-A form, profiles/r06_experiments.md; two months per tile 5.90 vs 5.78 ms per step).
 
 // indices the tiles cover (n, or n - 1 when the tail index is split off, see above)
 __host__ __device__ __forceinline__ int quad_main(int n) {
@@ -67,178 +62,6 @@ struct JobDesc {
   int ptile0;        // first partial slot of this job
 };
 
-// MM months x 64 rows of D per 256-thread workgroup (4 waves x 16 rows, 7 MFMA 16x16
-// accumulators per month).  Global->register prefetch of the next K step while this one is
-// computed from LDS (double-buffered), one barrier per K step; the epilogue's cross-wave sums
-// reuse the A staging buffer.
-template <int MM>
-__global__ __launch_bounds__(NT, MM == 1 ? 3 : 2) void quadform_kernel(
-    const double* __restrict__ D, int64_t ldD, const double* __restrict__ R,
-    const double* __restrict__ Bt, int64_t ldB, const JobDesc* __restrict__ jobs,
-    const int* __restrict__ tile_job, int L, double* __restrict__ partial) {
-  __shared__ double As[2][MM][BM][KS];
-  __shared__ double Bs[2][NCOL][KS];
-  static_assert(MM * NW * NCOL <= 2 * MM * BM * KS, "cross-wave sums must fit in the A buffers");
-  double (*red)[NW][NCOL] = reinterpret_cast<double (*)[NW][NCOL]>(&As[0][0][0][0]);
-
-  // tile_job[MM * tile + m] = job << 5 | row tile (month m of the tile; the jobs of one tile
-  // share the cell, so n and beta; -1 = no second month: the first is recomputed, not
-  // stored).  The host lists the tiles longest-first (all row tiles 0, then all 1, ...: the
-  // triangular K loop shrinks with the row tile); the partial slot stays ptile0 + rt.
-  const int tile = blockIdx.x;
-  int jm[MM];
-  bool live[MM];
-  int rt = 0;
-#pragma unroll
-  for (int m = 0; m < MM; ++m) {
-    const int tj = tile_job[MM * tile + m];
-    live[m] = tj >= 0;
-    jm[m] = (live[m] ? tj : tile_job[MM * tile]) >> 5;
-    if (m == 0) rt = tj & 31;
-  }
-  const JobDesc jd0 = jobs[jm[0]];
-  const int i0 = rt * BM;
-  const int nfull = jd0.n;
-  const int n = quad_main(nfull);                 // indices of the tiles and their K loop
-  const bool tail = n != nfull;
-  const double* Dm[MM];
-  const double* rm[MM];
-#pragma unroll
-  for (int m = 0; m < MM; ++m) {
-    const JobDesc jd = jobs[jm[m]];
-    Dm[m] = D + jd.d_off;
-    rm[m] = R + jd.r_off;
-  }
-  const double* bt = Bt + jd0.b_off;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-
-  double4_t acc[MM][NTILE];
-#pragma unroll
-  for (int m = 0; m < MM; ++m)
-#pragma unroll
-    for (int q = 0; q < NTILE; ++q) acc[m][q] = double4_t{0.0, 0.0, 0.0, 0.0};
-
-  // D_t is symmetric:  b'Db = sum_I b_I'(D_II b_I + 2 sum_{K>I} D_IK b_K).  A row tile I only
-  // walks K >= I, with the diagonal block weighted 1/2, so  acc = U_I / 2  and half the
-  // flops and D bytes of the full product are spent.
-  constexpr int AQ = (BM * BK) / NT;              // D elements per thread per K step per month
-  constexpr int BQ = (NCOL * BK + NT - 1) / NT;   // beta elements per thread per K step
-  double ra[MM][AQ], rb[BQ];
-  // Loads are unconditional (indices clamped into the matrix) and the masking / diagonal
-  // weight is applied when the registers are written to LDS: a load under a branch with its
-  // use in the same block made the compiler wait for every D element right after issuing it.
-  auto gload = [&](int k0) {
-#pragma unroll
-    for (int m = 0; m < MM; ++m)
-#pragma unroll
-      for (int q = 0; q < AQ; ++q) {
-        const int e = t + q * NT, i = e / BK, k = e % BK;
-        ra[m][q] = Dm[m][(int64_t)min(i0 + i, n - 1) * ldD + min(k0 + k, n - 1)];
-      }
-#pragma unroll
-    for (int q = 0; q < BQ; ++q) {
-      const int e = min(t + q * NT, NCOL * BK - 1), l = e / BK, k = e % BK;
-      rb[q] = bt[(int64_t)min(l, L - 1) * ldB + min(k0 + k, n - 1)];
-    }
-  };
-  auto sstore = [&](int buf, int k0) {
-    const double wdiag = (k0 < i0 + BM) ? 0.5 : 1.0;
-#pragma unroll
-    for (int m = 0; m < MM; ++m)
-#pragma unroll
-      for (int q = 0; q < AQ; ++q) {
-        const int e = t + q * NT, i = e / BK, k = e % BK;
-        As[buf][m][i][k] = (i0 + i < n && k0 + k < n) ? wdiag * ra[m][q] : 0.0;
-      }
-#pragma unroll
-    for (int q = 0; q < BQ; ++q) {
-      const int e = t + q * NT, l = e / BK, k = e % BK;
-      if (e < NCOL * BK) Bs[buf][l][k] = (l < L && k0 + k < n) ? rb[q] : 0.0;
-    }
-  };
-  auto compute = [&](int buf) {
-#pragma unroll
-    for (int kk = 0; kk < BK; kk += 4) {
-      double a[MM];
-#pragma unroll
-      for (int m = 0; m < MM; ++m) a[m] = As[buf][m][w * 16 + (lane & 15)][kk + (lane >> 4)];
-#pragma unroll
-      for (int q = 0; q < NTILE; ++q) {
-        const double b = Bs[buf][q * 16 + (lane & 15)][kk + (lane >> 4)];
-#pragma unroll
-        for (int m = 0; m < MM; ++m) acc[m][q] = mfma_f64_16x16x4(a[m], b, acc[m][q]);
-      }
-    }
-  };
-  gload(i0);
-  sstore(0, i0);
-  __syncthreads();
-  int buf = 0;
-  for (int k0 = i0;;) {
-    const bool more = k0 + BK < n;
-    if (more) gload(k0 + BK);
-    compute(buf);
-    if (!more) break;
-    sstore(buf ^ 1, k0 + BK);
-    __syncthreads();
-    k0 += BK;
-    buf ^= 1;
-  }
-  __syncthreads();                            // red reuses As
-
-  // tail column n: U[i][l] += D[i][n] b_l[n] (K block above every row tile: weight 1)
-  if (tail) {
-#pragma unroll
-    for (int q = 0; q < NTILE; ++q) {
-      const int l = min(q * 16 + (lane & 15), L - 1);
-      const double bt_l = bt[(int64_t)l * ldB + n];
-#pragma unroll
-      for (int m = 0; m < MM; ++m)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          const int gi = min(i0 + w * 16 + PFML_F64_CROW(lane, rr), n - 1);
-          acc[m][q][rr] = fma(Dm[m][(int64_t)gi * ldD + n], bt_l, acc[m][q][rr]);
-        }
-    }
-  }
-
-  // epilogue: sum over this wave's 16 rows of  beta_l[i] * (r_i - 1/2 U[i][l])
-#pragma unroll
-  for (int q = 0; q < NTILE; ++q) {
-    const int l = q * 16 + (lane & 15);
-    double b[4];
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      const int gi = i0 + w * 16 + PFML_F64_CROW(lane, rr);
-      b[rr] = (gi < n && l < L) ? bt[(int64_t)l * ldB + gi] : 0.0;
-    }
-#pragma unroll
-    for (int m = 0; m < MM; ++m) {
-      double s = 0.0;
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int gi = i0 + w * 16 + PFML_F64_CROW(lane, rr);
-        if (gi < n && l < L) s += b[rr] * (rm[m][gi] - acc[m][q][rr]);   // acc = U / 2
-      }
-      // lanes l, l+16, l+32, l+48 share the column
-      s += __shfl_xor(s, 16, 64);
-      s += __shfl_xor(s, 32, 64);
-      if (lane < 16) red[m][w][l] = s;
-    }
-  }
-  __syncthreads();
-  if (t < NCOL) {
-#pragma unroll
-    for (int m = 0; m < MM; ++m) {
-      if (!live[m]) continue;
-      double s = 0.0;
-#pragma unroll
-      for (int q = 0; q < NW; ++q) s += red[m][q][t];
-      if (t < L) partial[(int64_t)(jobs[jm[m]].ptile0 + rt) * L + t] = s;
-    }
-  }
-}
-
 // Direct-A form.  A wave's D rows are private to it (16 rows per wave, the tile's four waves
 // disjoint), so D needs no LDS staging at all: every lane loads its own MFMA A fragments
 // straight from global memory into registers, two K steps ahead (a ring of three 4-double
@@ -251,8 +74,7 @@ __global__ __launch_bounds__(NT, MM == 1 ? 3 : 2) void quadform_kernel(
 //   beta image: row l (16 doubles = 32 banks), element k at l * 16 + (k ^ g(l)),
 //   g(l) = (m & 3) | ((m & 4) << 1), m = (l >> 1) & 7: the fragment reads (16 rows x 2 lane
 //   groups per half-wave) hit all 64 banks, the staging writes 2-way at most.
-// Same tile grid, partial slots and epilogue as quadform_kernel<1>; the k summation order
-// differs (bits differ from that form, same on every rank count).
+// The k summation order is fixed by this layout alone (the same bits on every rank count).
 __device__ __forceinline__ int qd_swz(int l) {
   const int m = (l >> 1) & 7;
   return (m & 3) | ((m & 4) << 1);
@@ -471,7 +293,7 @@ __device__ __forceinline__ void quad_direct_body(
     // leaves the D loads in flight (vmcnt counts in issue order)
     if (more) bload(k0 + BK);
     if (st + 2 < nst) dload((cur + 2) % 3, k0 + 2 * BK);
-    // the diagonal block (k < i0 + 64) weighted 1/2: acc = U / 2 (see quadform_kernel)
+    // the diagonal block (k < i0 + 64) weighted 1/2: acc = U / 2 (D_t is symmetric, see top)
     const double wd = (k0 < i0 + BM) ? 0.5 : 1.0;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -587,33 +409,28 @@ extern "C" int pfml_quadform_aligned(int n, int L, int64_t ldD, int64_t ldB) {
   return quad_aligned(n, L, ldD, ldB) ? 1 : 0;
 }
 
-// tile_job: mm (1 or 2; 1 for the direct and pipelined forms, mm = 3 / 4 / 5) int32 entries
-// per tile.
+// tile_job: one int32 per tile, job << 5 | row tile.  form: 3 = the direct-A form for every
+// tile; 4 = the pipelined form, every job of the launch aligned (pfml_quadform_aligned); 5 =
+// the pipelined form for the aligned jobs and the direct form's loop for the rest.  The
+// argument keeps the position and the values it had when 1 / 2 meant the retired LDS-staged
+// forms (months per tile), so a library built before their removal still loads under
+// PFML_HIP_LIB for an A/B against this one; 1 / 2 are refused here.
 extern "C" hipError_t pfml_quadform(const double* D, int64_t ldD, const double* R,
                                     const double* Bt, int64_t ldB, const void* jobs, int njobs,
-                                    const int* tile_job, int ntiles, int mm, int L,
+                                    const int* tile_job, int ntiles, int form, int L,
                                     double* partial, double* obj, hipStream_t st) {
   if (njobs <= 0) return hipSuccess;
-  // mm: months per tile (1 / 2); 3 = the direct-A form on the one-month tile list; 4 = the
-  // pipelined form, every job of the launch aligned (pfml_quadform_aligned); 5 = the
-  // pipelined form for the aligned jobs and the direct form's loop for the rest
-  if (L > NCOL || mm < 1 || mm > 5) return hipErrorInvalidValue;
+  if (L > NCOL || form < 3 || form > 5) return hipErrorInvalidValue;
   const JobDesc* jd = static_cast<const JobDesc*>(jobs);
-  if (mm >= 4) {
+  if (form >= 4) {
     hipLaunchKernelGGL(quadform_pipe_kernel, dim3(ntiles), dim3(NT), 0, st, D, ldD, R, Bt, ldB,
                        jd, tile_job, L, partial);
-    if (mm == 5)
+    if (form == 5)
       hipLaunchKernelGGL(quadform_rest_kernel, dim3(ntiles), dim3(NT), 0, st, D, ldD, R, Bt,
                          ldB, jd, tile_job, L, partial);
-  } else if (mm == 3)
+  } else
     hipLaunchKernelGGL(quadform_direct_kernel, dim3(ntiles), dim3(NT), 0, st, D, ldD, R, Bt, ldB,
                        jd, tile_job, L, partial);
-  else if (mm == 2)
-    hipLaunchKernelGGL(quadform_kernel<2>, dim3(ntiles), dim3(NT), 0, st, D, ldD, R, Bt, ldB, jd,
-                       tile_job, L, partial);
-  else
-    hipLaunchKernelGGL(quadform_kernel<1>, dim3(ntiles), dim3(NT), 0, st, D, ldD, R, Bt, ldB, jd,
-                       tile_job, L, partial);
   hipLaunchKernelGGL(quadform_reduce_kernel, dim3(njobs), dim3(128), 0, st, partial, jd, njobs, L,
                      D, ldD, R, Bt, ldB, obj);
   return hipGetLastError();

@@ -40,9 +40,8 @@ def _declare_hip(lib):
     lib.pfml_quadform_rows_per_tile.restype = I
     lib.pfml_quadform_row_tiles.argtypes = [I]
     lib.pfml_quadform_row_tiles.restype = I
-    if hasattr(lib, "pfml_quadform_aligned"):      # absent from an older PFML_HIP_LIB build
-        lib.pfml_quadform_aligned.argtypes = [I, I, L, L]
-        lib.pfml_quadform_aligned.restype = I
+    lib.pfml_quadform_aligned.argtypes = [I, I, L, L]
+    lib.pfml_quadform_aligned.restype = I
     lib.pfml_segsum.argtypes = [P, L, P, P, I, P, P]
     lib.pfml_segsum.restype = I
     lib.pfml_spd_inverse.argtypes = [P, I, L, L, I, P, P, P]

@@ -7,8 +7,8 @@ PFML_Search_Coef.py:131-133; r'b - 1/2 b'Db per month, PFML_hp_reals.py:94).
 from __future__ import annotations
 
 import ctypes as C
-
 import os
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -238,7 +238,6 @@ class _HostClock:
     queued work)."""
 
     def __init__(self):
-        import os
         import time
         v = os.environ.get("PFML_HOST_TIMING", "")
         self.on = bool(v)
@@ -289,12 +288,55 @@ def _work_doubles(n_arr: np.ndarray, L: int) -> np.ndarray:
 
 COOP_KMAX = 16          # workgroups per cell of the cooperative band reduction (wgmap: 4 bits)
 COOP_SYNC_WORDS = 32    # csrc/ridge_band.hip COOP_SYNC: int32 sync words per cell
-
-
 COOP_BIG_SHARE = 0.42   # share of the CUs the largest cells' cooperative launch gets (coop_k)
+QUAD_DIRECT, QUAD_PIPE, QUAD_PIPE_REST = 3, 4, 5     # csrc/quadform.hip pfml_quadform's `form`
 
 
-def coop_k(cell_n: np.ndarray, ncu: int) -> np.ndarray:
+@dataclass(frozen=True)
+class Switches:
+    """Every environment variable that shapes a grid-step launch, read in one place
+    (``switches()``): per field the default, and the variable that selects the other A/B arm.
+
+    coop_k         ``coop_k``'s policy; PFML_COOP_K=k (not empty): k workgroups per largest cell
+    coop_solo      a launch whose cells all have K = 1 on the solo kernel; PFML_COOP_SOLO=0: not
+    coop_spin_max  the library's ~1 s poll bound of the cooperative waits; PFML_COOP_SPIN_MAX=n: n
+    bt_classes     a back-transform instance per size class; PFML_BT_CLASSES=0: 8 waves for all
+    bt_wy          n > 1024 cells on the blocked-WY MFMA back-transform; PFML_RIDGE_BT_WY=0: generic
+    two_streams    the largest cells' group and the rest on two streams; PFML_RIDGE_STREAMS=1: one
+    quad_direct    the pipelined utilities form; PFML_QUAD_DIRECT not empty: the direct-A form
+    quad_xcd       every utilities tile of a cell on one XCD (``_xcd_affine``); PFML_QUAD_XCD=0: not
+
+    PFML_RIDGE_STREAMS means one stream at any value but empty or 2.  Retired, ValueError both:
+    PFML_QUAD_DIRECT=0, PFML_QUAD_MM=2 - the removed LDS-staged forms (PFML_QUAD_MM=1: a no-op).
+    """
+    coop_k: int | None = None
+    coop_solo: bool = True
+    coop_spin_max: int = 0
+    bt_classes: bool = True
+    bt_wy: bool = True
+    two_streams: bool = True
+    quad_direct: bool = False
+    quad_xcd: bool = True
+
+
+def switches() -> Switches:
+    """The launch switches as the environment sets them now."""
+    env = os.environ.get
+    if env("PFML_QUAD_DIRECT") == "0" or env("PFML_QUAD_MM") == "2":
+        raise ValueError("PFML_QUAD_DIRECT=0 and PFML_QUAD_MM=2 are retired: the LDS-staged "
+                         "utilities forms they selected were removed")
+    return Switches(
+        coop_k=int(env("PFML_COOP_K")) if env("PFML_COOP_K") else None,
+        coop_solo=env("PFML_COOP_SOLO", "1") != "0",
+        coop_spin_max=int(env("PFML_COOP_SPIN_MAX", "0") or 0),
+        bt_classes=env("PFML_BT_CLASSES", "1") != "0",
+        bt_wy=env("PFML_RIDGE_BT_WY", "1") != "0",
+        two_streams=(env("PFML_RIDGE_STREAMS") or "2").strip() == "2",
+        quad_direct=env("PFML_QUAD_DIRECT", "") != "",
+        quad_xcd=env("PFML_QUAD_XCD", "1") != "0")
+
+
+def coop_k(cell_n: np.ndarray, ncu: int, sw: Switches | None = None) -> np.ndarray:
     """Workgroups per cell of the cooperative band reduction.
 
     The largest-n cells of a launch are the p = 512 cells (n > 256: 32 panels, the grid step's
@@ -306,15 +348,15 @@ def coop_k(cell_n: np.ndarray, ncu: int) -> np.ndarray:
     W = 1 / 2 / 4 / 8 ranks (106 / 53 / 27 / 13 big cells per rank), i.e. ~106 of 256 CUs for the
     big cells whatever W - giving them all the CUs the small cells leave (K = 16 at W = 8) was
     27 % slower per rank.  The betas do not depend on K (bitwise: see band_coop_kernel), only
-    the time does.  PFML_COOP_K=k forces k for the largest cells."""
+    the time does.  PFML_COOP_K=k (``sw.coop_k``) forces k for the largest cells."""
+    sw = sw or switches()
     n = np.asarray(cell_n)
     k = np.ones(len(n), dtype=np.int64)
     if not len(n):
         return k
     big = n == n.max()
-    v = os.environ.get("PFML_COOP_K")
-    if v:
-        kb = int(v)
+    if sw.coop_k is not None:
+        kb = sw.coop_k
     elif int(n.max()) > 256:
         kb = int(round(COOP_BIG_SHARE * ncu / int(big.sum())))
     else:
@@ -364,7 +406,8 @@ def num_cus(dev) -> int:
     return max(1, _NCU[key] // ranks_per_device())
 
 
-def ridge_plan(P: int, L: int, cell_src, cell_n, cell_scale, ncu: int = 256) -> dict:
+def ridge_plan(P: int, L: int, cell_src, cell_n, cell_scale, ncu: int = 256,
+               sw: Switches | None = None) -> dict:
     """Host-side descriptors of one ridge-grid launch (CELL_DTYPE, big cells first) and the
     workgroup map of the cooperative reduction (``ncu``: the device's CUs)."""
     lib = nat.hip_lib()
@@ -389,7 +432,7 @@ def ridge_plan(P: int, L: int, cell_src, cell_n, cell_scale, ncu: int = 256) -> 
     desc = desc[order]
     wsz = wsz[order]
     desc["work"] = np.concatenate([[0], np.cumsum(wsz)[:-1]])
-    wgmap = coop_wgmap(coop_k(desc["n"], ncu))
+    wgmap = coop_wgmap(coop_k(desc["n"], ncu, sw))
     # host copy of n in plan order: the back-transform's instance per size class
     n_host = np.ascontiguousarray(desc["n"], dtype=np.int32)
     return {"desc": desc, "work": int(wsz.sum()), "nmax": int(cell_n.max()), "nc": nc,
@@ -441,14 +484,6 @@ def repairs_done() -> int:
     return int(sum(int(c.item()) for c in LAST_REPAIRS))
 
 
-def _n_host_ptr(plan: dict):
-    """Host pointer to the plan's per-cell n (read during the launch call only);
-    PFML_BT_CLASSES=0: None, every cell on the 8-wave back-transform."""
-    if os.environ.get("PFML_BT_CLASSES", "1") == "0" or "n_host" not in plan:
-        return None
-    return plan["n_host"].ctypes.data
-
-
 def band_path(plan: dict) -> bool:
     """True when the launch takes the band path (ridge_band.hip, n <= 528), whose non-SPD
     lambdas are repaired in the band domain inside the launch; the tridiagonal path
@@ -460,11 +495,13 @@ def band_path(plan: dict) -> bool:
 
 def ridge_launch(plan: dict, d_desc: torch.Tensor, SD: torch.Tensor, Sr: torch.Tensor,
                  lv: torch.Tensor, beta: torch.Tensor, repair: bool = True,
-                 d_wgmap: torch.Tensor | None = None) -> torch.Tensor | None:
+                 d_wgmap: torch.Tensor | None = None,
+                 sw: Switches | None = None) -> torch.Tensor | None:
     """Queue one ridge-grid launch; returns the device count of non-SPD systems re-solved by
     the band path's pivoted banded LU (kernel 2b of ridge_band.hip), None when the launch has
     no in-band repair (``repair=False`` or the tridiagonal path).  ``d_wgmap``: the device
     copy of plan["wgmap"] (the cooperative band reduction's workgroup map)."""
+    sw = sw or switches()
     P = SD.shape[-1]
     L = int(lv.numel())
     work = torch.empty(plan["work"], dtype=torch.float64, device=SD.device)
@@ -475,21 +512,15 @@ def ridge_launch(plan: dict, d_desc: torch.Tensor, SD: torch.Tensor, Sr: torch.T
         lst = torch.empty(plan["nc"] * L, dtype=torch.int32, device=SD.device)
     if band and d_wgmap is None:
         raise ValueError("ridge_launch: the cooperative reduction needs the device wgmap")
-    if not band:
-        # PFML_RIDGE_BT_WY=0: cells with n > 1024 on the generic back-transform (the A/B arm of
-        # tools/bench_large_p.py) instead of the blocked MFMA kernel
-        nat.hip_lib().pfml_ridge_set_bt_wy(int(os.environ.get("PFML_RIDGE_BT_WY", "1") != "0"))
+    _apply_switches(sw, band)
     sync = (torch.empty(plan["nc"] * COOP_SYNC_WORDS, dtype=torch.int32, device=SD.device)
             if band else None)
     if band:
-        _spin_from_env()
-        # PFML_COOP_SOLO=0: the general cooperative kernel also for a launch whose cells all
-        # have K = 1 (the A/B arm of the solo instance; absent from an older PFML_HIP_LIB build)
-        if hasattr(nat.hip_lib(), "pfml_coop_set_solo"):
-            nat.hip_lib().pfml_coop_set_solo(int(os.environ.get("PFML_COOP_SOLO", "1") != "0"))
         # every launch's sync words are kept until the next grid search starts (the big and the
         # small cells' launches run on two streams: neither may hide the other's timeouts)
         LAST_COOP_SYNC.append(sync)
+    # host pointer to the plan's per-cell n (read during the launch call only)
+    n_host = plan["n_host"].ctypes.data if sw.bt_classes else None
     nat.check(nat.hip_lib().pfml_ridge_grid(SD.data_ptr(), P, Sr.data_ptr(), d_desc.data_ptr(),
                                             plan["nc"], plan["nmax"], lv.data_ptr(), L,
                                             work.data_ptr(), beta.data_ptr(), beta.shape[-1],
@@ -499,7 +530,7 @@ def ridge_launch(plan: dict, d_desc: torch.Tensor, SD: torch.Tensor, Sr: torch.T
                                             d_wgmap.data_ptr() if band else None,
                                             len(plan["wgmap"]) if band else 0,
                                             sync.data_ptr() if band else None,
-                                            _n_host_ptr(plan), nat.stream_of(SD)),
+                                            n_host, nat.stream_of(SD)),
               "pfml_ridge_grid")
     return count
 
@@ -524,20 +555,23 @@ def coop_errors() -> int:
                    for s in LAST_COOP_SYNC))
 
 
-_SPIN_ENV: list = []
+_SPIN_OVERRIDE = [0]
 
 
 def set_coop_spin_max(n: int) -> None:
-    """Poll bound of the cooperative reduction's waits for later launches (0: the default,
-    ~1 s).  Tests lower it to force timeouts; ``PFML_COOP_SPIN_MAX`` sets it before the first
-    launch."""
-    _SPIN_ENV[:] = [True]
-    nat.hip_lib().pfml_coop_set_spin_max(int(n))
+    """Poll bound of the cooperative reduction's waits for later launches (tests lower it to
+    force timeouts); it wins over ``PFML_COOP_SPIN_MAX`` until it is called with 0."""
+    _SPIN_OVERRIDE[0] = int(n)
 
 
-def _spin_from_env() -> None:
-    if not _SPIN_ENV:
-        set_coop_spin_max(int(os.environ.get("PFML_COOP_SPIN_MAX", "0") or 0))
+def _apply_switches(sw: Switches, band: bool) -> None:
+    """Set the switches the library keeps as host globals, read by the next launch call."""
+    lib = nat.hip_lib()
+    if band:
+        lib.pfml_coop_set_spin_max(_SPIN_OVERRIDE[0] or sw.coop_spin_max)
+        lib.pfml_coop_set_solo(int(sw.coop_solo))
+    else:
+        lib.pfml_ridge_set_bt_wy(int(sw.bt_wy))
 
 
 def ridge_grid(SD: torch.Tensor, Sr: torch.Tensor, cell_src: np.ndarray, cell_n: np.ndarray,
@@ -553,7 +587,8 @@ def ridge_grid(SD: torch.Tensor, Sr: torch.Tensor, cell_src: np.ndarray, cell_n:
     L = int(lvec.numel())
     nc = len(cell_src)
     # (the plan first: a cell above the device limit is refused before anything is queued)
-    plan = (ridge_plan(P, L, cell_src, cell_n, cell_scale, ncu=num_cus(SD.device))
+    sw = switches()
+    plan = (ridge_plan(P, L, cell_src, cell_n, cell_scale, ncu=num_cus(SD.device), sw=sw)
             if nc and nat.is_device(SD) else None)
     beta = torch.zeros((nc, L, P), dtype=SD.dtype, device=SD.device)
     if nc == 0:
@@ -563,7 +598,7 @@ def ridge_grid(SD: torch.Tensor, Sr: torch.Tensor, cell_src: np.ndarray, cell_n:
         d_desc, d_wg = upload([plan["desc"], plan["wgmap"]], SD.device)
         lv = lvec.to(device=SD.device, dtype=torch.float64).contiguous()
         SDc, Src = SD.contiguous(), Sr.contiguous()
-        count = ridge_launch(plan, d_desc, SDc, Src, lv, beta, repair=repair, d_wgmap=d_wg)
+        count = ridge_launch(plan, d_desc, SDc, Src, lv, beta, repair, d_wg, sw)
         if repair:
             LAST_REPAIRS[:] = [count if count is not None
                                else repair_launch(plan, d_desc, SDc, Src, lv, beta)]
@@ -617,14 +652,6 @@ def _side_stream(dev: torch.device, k: int = 0) -> torch.cuda.Stream:
     return _SIDE[key]
 
 
-def two_streams() -> bool:
-    """The largest cells' ridge group and the rest on two streams (default; the small cells'
-    chain fills the CUs the big cells leave idle).  PFML_RIDGE_STREAMS=1 puts them on one."""
-    import os
-    v = os.environ.get("PFML_RIDGE_STREAMS")
-    return (v.strip() == "2") if v else True
-
-
 _UTIL_PLANS: dict = {}
 
 BAND_NMAX = 528         # csrc/ridge_band.hip BNMAX (pfml_ridge_band_nmax): the band path's largest n
@@ -649,13 +676,13 @@ def ridge_groups(cell_n, band_nmax: int = BAND_NMAX) -> list:
 
 
 def _utilities_plan(P: int, L: int, dev, cell_src, cell_n, cell_scale, job_cell, job_month,
-                    job_n, split: bool = True) -> dict:
+                    job_n, split: bool = True, sw: Switches | None = None) -> dict:
     """Launch plan of ridge_utilities on a device, cached: the descriptors depend only on the
-    grid's shape (cells, jobs, P, L), so repeated grid searches (every step of a run, every
-    benchmark step) reuse the uploaded device copies and skip all host planning.  Each group's
-    cells / jobs write straight into the full beta / obj arrays (global out offsets)."""
-    key = (P, L, str(dev), split, os.environ.get("PFML_QUAD_MM", "1"),
-           os.environ.get("PFML_COOP_K", ""),
+    grid's shape (cells, jobs, P, L) and the switches, so repeated grid searches (every step of
+    a run, every benchmark step) reuse the uploaded device copies and skip all host planning.
+    Each group's cells / jobs write straight into the full beta / obj arrays (global offsets)."""
+    sw = sw or switches()
+    key = (sw, P, L, str(dev), split,
            cell_src.tobytes(), cell_n.tobytes(), cell_scale.tobytes(),
            job_cell.tobytes(), job_month.tobytes(), job_n.tobytes())
     hit = _UTIL_PLANS.get(key)
@@ -675,10 +702,10 @@ def _utilities_plan(P: int, L: int, dev, cell_src, cell_n, cell_scale, job_cell,
         grp = np.zeros(len(cell_n), dtype=bool)
         grp[cells] = True
         jobs = np.nonzero(grp[job_cell])[0]
-        rp = ridge_plan(P, L, cell_src[cells], cell_n[cells], cell_scale[cells], ncu=num_cus(dev))
+        rp = ridge_plan(P, L, cell_src[cells], cell_n[cells], cell_scale[cells], num_cus(dev), sw)
         # ridge_plan orders cells big-first and numbers outputs 0..: map to global rows
         rp["desc"]["out"] = cells[rp["desc"]["out"] // (L * P)].astype(np.int64) * L * P
-        qp = quad_plan(P, L, P, job_cell[jobs], job_month[jobs], job_n[jobs], job_out=jobs)
+        qp = quad_plan(P, L, P, job_cell[jobs], job_month[jobs], job_n[jobs], job_out=jobs, sw=sw)
         groups.append((cells, jobs, rp, qp))
         arrays += [rp["desc"], qp["desc"], qp["tile_job"], rp["wgmap"]]
     dv = upload(arrays, dev)                     # all descriptors, one async copy
@@ -732,7 +759,8 @@ def ridge_utilities(SD: torch.Tensor, Sr: torch.Tensor, cell_src, cell_n, cell_s
     if not nat.is_device(SD):
         beta = ridge_grid(SD, Sr, cell_src, cell_n, cell_scale, lvec)
         return beta, quadform_utilities(D, R, beta, job_cell, job_month, job_n)
-    split = two_streams() and len(np.unique(cell_n)) >= 2
+    sw = switches()
+    split = sw.two_streams and len(np.unique(cell_n)) >= 2
     reset_coop_sync()
     th = _HostClock()
     S, P, _ = SD.shape
@@ -741,7 +769,7 @@ def ridge_utilities(SD: torch.Tensor, Sr: torch.Tensor, cell_src, cell_n, cell_s
     nc = len(cell_src)
     dev = SD.device
     plan = _utilities_plan(P, L, dev, cell_src, cell_n, cell_scale, job_cell, job_month, job_n,
-                           split=split)
+                           split=split, sw=sw)
     th("plans")
     # every [L, P] block is written whole by the ridge grid (zero padding past n included), so
     # no fill on the stream the big cells' chain forks from
@@ -761,9 +789,9 @@ def ridge_utilities(SD: torch.Tensor, Sr: torch.Tensor, cell_src, cell_n, cell_s
         stream = streams[gi]
         _, _, rp, qp = plan["groups"][gi]
         with torch.cuda.stream(stream):
-            cnt = ridge_launch(rp, dv[4 * gi], SD, Sr, lv, beta, d_wgmap=dv[4 * gi + 3])
+            cnt = ridge_launch(rp, dv[4 * gi], SD, Sr, lv, beta, d_wgmap=dv[4 * gi + 3], sw=sw)
             counts.append(cnt if cnt is not None else repair_launch(rp, dv[4 * gi], SD, Sr, lv, beta))
-            quad_launch(qp, dv[4 * gi + 1], dv[4 * gi + 2], D, R, beta, obj)
+            quad_launch(qp, dv[4 * gi + 1], dv[4 * gi + 2], D, R, beta, obj, sw=sw)
     th("launch")
     for st in streams:
         if st == cur:
@@ -775,9 +803,12 @@ def ridge_utilities(SD: torch.Tensor, Sr: torch.Tensor, cell_src, cell_n, cell_s
     return beta, obj
 
 
-def quad_plan(P: int, L: int, Pb: int, job_cell, job_month, job_n, job_out=None) -> dict:
-    """Host-side descriptors of one utilities launch (JOB_DTYPE + row-tile -> job map).
-    ``job_out``: row of each job in the obj array the launch writes (default: 0..nj-1)."""
+def quad_plan(P: int, L: int, Pb: int, job_cell, job_month, job_n, job_out=None,
+              sw: Switches | None = None) -> dict:
+    """Host-side descriptors of one utilities launch: JOB_DTYPE per job and ``tile_job``, one
+    int32 ``job << 5 | row tile`` per 64-row tile in launch order.  ``job_out``: row of each
+    job in the obj array the launch writes (default: 0..nj-1)."""
+    sw = sw or switches()
     lib = nat.hip_lib()
     if lib.pfml_quadform_job_desc_size() != JOB_DTYPE.itemsize:
         raise RuntimeError("JobDesc layout mismatch between python and libpfml_hip")
@@ -798,43 +829,23 @@ def quad_plan(P: int, L: int, Pb: int, job_cell, job_month, job_n, job_out=None)
     desc["ptile0"] = pt0
     if nj and int(ntile.max()) > 32:
         raise ValueError("quad_plan: more than 32 row tiles per job (n > 32 * 64)")
-    # a tile covers `mm` jobs of ONE cell (same beta, same n: its validation months), so the
-    # staged beta K-tiles feed mm D tiles; an odd job out gets -1 in the spare entries
-    # (2 months per tile: measured 5.90 vs 5.78 ms per grid step on MI355X - fewer resident
-    # workgroups cost more than the halved beta traffic saves - so 1 is the default)
-    mm = 2 if os.environ.get("PFML_QUAD_MM", "1") == "2" else 1
     jc = np.asarray(job_cell, np.int64)
-    # jobs grouped by (cell, n), stable: a tile's jobs share beta AND the row / K extent
+    # jobs by (cell, n), stable: the validation months of a cell follow each other
     by_cell = np.lexsort((np.arange(nj), job_n, jc))
-    key = jc * 65536 + job_n.astype(np.int64)
-    groups = []
-    i = 0
-    while i < nj:
-        c = key[by_cell[i]]
-        k = i
-        while k < nj and key[by_cell[k]] == c and k - i < mm:
-            k += 1
-        groups.append(by_cell[i:k])
-        i = k
-    ng = len(groups)
-    gj = np.full((ng, mm), -1, dtype=np.int64)
-    for gi, grp in enumerate(groups):
-        gj[gi, :len(grp)] = grp
-    gnt = ntile[gj[:, 0]] if ng else np.zeros(0, np.int64)
-    # tiles longest-first (row tile 0 of every group, then row tile 1, ...): the triangular K
+    jnt = ntile[by_cell]
+    # tiles longest-first (row tile 0 of every job, then row tile 1, ...): the triangular K
     # loop of row tile rt is ~(n - 64 rt) long, so the launch ends on the short tiles;
-    # entry = job << 5 | rt (the kernel writes partial slot ptile0 + rt of each live job)
-    gg = np.repeat(np.arange(ng, dtype=np.int64), gnt)
-    g0 = np.concatenate([[0], np.cumsum(gnt)[:-1]]).astype(np.int64) if ng else np.zeros(0, np.int64)
-    rt = np.arange(len(gg), dtype=np.int64) - np.repeat(g0, gnt)
-    order = np.lexsort((gg, rt))
-    gg, rt = gg[order], rt[order]
-    jobs_t = gj[gg]                                      # [ntiles, mm]
-    if len(jobs_t) and os.environ.get("PFML_QUAD_XCD", "1") != "0":
-        jobs_t, rt = _xcd_affine(jobs_t, rt, jc[jobs_t[:, 0]])
-    tile_job = np.where(jobs_t >= 0, (jobs_t << 5) | rt[:, None], -1).astype(np.int32).reshape(-1)
-    return {"desc": desc, "tile_job": tile_job, "nj": nj, "ntiles": len(gg),
-            "nslots": int(ntile.sum()), "mm": mm}
+    # entry = job << 5 | rt (the kernel writes partial slot ptile0 + rt of the job)
+    jt = np.repeat(by_cell, jnt)
+    rt = np.arange(len(jt), dtype=np.int64) - np.repeat(np.cumsum(jnt) - jnt, jnt)
+    order = np.argsort(rt, kind="stable")
+    jt, rt = jt[order], rt[order]
+    if len(jt) and sw.quad_xcd:
+        jt, rt = _xcd_affine(jt, rt, jc[jt])
+    tile_job = ((jt << 5) | rt).astype(np.int32)
+    aligned = all(lib.pfml_quadform_aligned(n, L, P, Pb) for n in tiles_of)
+    return {"desc": desc, "tile_job": tile_job, "nj": nj, "ntiles": len(jt),
+            "nslots": int(ntile.sum()), "pipe": QUAD_PIPE if aligned else QUAD_PIPE_REST}
 
 
 NXCD = 8   # MI355X: workgroup b of a launch is dispatched to XCD b mod 8
@@ -863,34 +874,22 @@ def _xcd_affine(jobs_t: np.ndarray, rt: np.ndarray, cell: np.ndarray):
 
 
 def quad_launch(plan: dict, d_desc: torch.Tensor, d_tj: torch.Tensor, D: torch.Tensor,
-                R: torch.Tensor, beta: torch.Tensor, obj: torch.Tensor) -> None:
+                R: torch.Tensor, beta: torch.Tensor, obj: torch.Tensor,
+                sw: Switches | None = None) -> None:
+    """Queue one utilities launch (csrc/quadform.hip) of a ``quad_plan`` made for these P, L
+    and beta row stride.  Default: the pipelined loop for the aligned jobs - QUAD_PIPE when
+    every job is aligned, as in production, else QUAD_PIPE_REST, which adds a launch of the
+    direct form's loop for the rest.  ``sw.quad_direct``: the direct form for every tile."""
+    sw = sw or switches()
     if plan["nj"] == 0:
         return
     P = D.shape[-1]
     L, Pb = beta.shape[1], beta.shape[2]
-    nt = plan["ntiles"]
     partial = torch.empty((plan["nslots"], L), dtype=torch.float64, device=D.device)
-    # one-month tiles take the direct-A form (csrc/quadform.hip: D fragments straight to
-    # registers two steps ahead, only beta through LDS), by default with the pipelined loop
-    # for the aligned jobs (quadform_pipe_kernel: mm = 4 when every job of the launch is
-    # aligned, as in production; else mm = 5, which adds a launch of the direct form's loop
-    # for the rest).  PFML_QUAD_DIRECT=1 selects the direct form for every tile
-    # (quadform_direct_kernel, mm = 3), PFML_QUAD_DIRECT=0 the LDS-staged form.
-    mm = plan["mm"]
-    if mm == 1:
-        direct = os.environ.get("PFML_QUAD_DIRECT", "")
-        if direct == "":
-            key = ("aligned", L, P, Pb)
-            if key not in plan:
-                lib = nat.hip_lib()
-                plan[key] = all(lib.pfml_quadform_aligned(int(v), L, P, Pb)
-                                for v in np.unique(plan["desc"]["n"]))
-            mm = 4 if plan[key] else 5
-        elif direct != "0":
-            mm = 3
+    form = QUAD_DIRECT if sw.quad_direct else plan["pipe"]
     nat.check(nat.hip_lib().pfml_quadform(D.data_ptr(), P, R.data_ptr(), beta.data_ptr(), Pb,
-                                          d_desc.data_ptr(), plan["nj"], d_tj.data_ptr(), nt,
-                                          mm, L,
+                                          d_desc.data_ptr(), plan["nj"], d_tj.data_ptr(),
+                                          plan["ntiles"], form, L,
                                           partial.data_ptr(), obj.data_ptr(),
                                           nat.stream_of(D)), "pfml_quadform")
 
@@ -906,9 +905,10 @@ def quadform_utilities(D: torch.Tensor, R: torch.Tensor, beta: torch.Tensor,
     if nj == 0:
         return obj
     if nat.is_device(D):
-        plan = quad_plan(P, L, Pb, job_cell, job_month, job_n)
+        sw = switches()
+        plan = quad_plan(P, L, Pb, job_cell, job_month, job_n, sw=sw)
         d_desc, d_tj = upload([plan["desc"], plan["tile_job"]], D.device)
-        quad_launch(plan, d_desc, d_tj, D.contiguous(), R.contiguous(), beta.contiguous(), obj)
+        quad_launch(plan, d_desc, d_tj, D.contiguous(), R.contiguous(), beta.contiguous(), obj, sw)
         return obj
     for j in range(nj):
         n, m, c = int(job_n[j]), int(job_month[j]), int(job_cell[j])

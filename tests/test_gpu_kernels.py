@@ -887,9 +887,10 @@ def test_chunked_window_sums_world_bitwise(gpu):
             assert torch.equal(got[y][1], ref[y][1]), (W, y)
 
 
-def test_quadform_two_months_bitwise(gpu, monkeypatch):
-    """Two validation months per workgroup (shared beta tiles) give BITWISE the utilities of
-    one month per workgroup (same per-month MFMA order), incl. an odd job out and n < 64."""
+def test_quadform_default_equals_direct_odd_jobs(gpu, monkeypatch):
+    """The default (pipelined) utilities form and the direct form (PFML_QUAD_DIRECT=1) give
+    BITWISE the same utilities, both the CPU oracle's, on a launch with an odd job out, n = 33
+    < 64 and the n = 65 tail split."""
     from pfml.ops.ridge import quadform_utilities
     P, L = 130, 101
     D = _spd_stack(7, P, n_obs=150, seed=95) / 150
@@ -899,27 +900,26 @@ def test_quadform_two_months_bitwise(gpu, monkeypatch):
     jm = np.array([0, 1, 2, 3, 4, 5, 6, 0, 1])
     jn = np.array([130, 130, 130, 65, 65, 33, 33, 33, 33])
     args = (D.to(gpu), R.to(gpu), beta.to(gpu), jc, jm, jn)
-    monkeypatch.setenv("PFML_QUAD_DIRECT", "0")
-    monkeypatch.setenv("PFML_QUAD_MM", "1")
-    one = quadform_utilities(*args).cpu()
-    monkeypatch.setenv("PFML_QUAD_MM", "2")
-    two = quadform_utilities(*args).cpu()
-    assert torch.equal(one, two)
-    ref = quadform_utilities(D, R, beta, jc, jm, jn)
-    assert torch.allclose(two, ref, rtol=1e-11, atol=1e-11)
-    # the direct-A form (default for one-month tiles): its own k order, same oracle
-    monkeypatch.setenv("PFML_QUAD_MM", "1")
+    monkeypatch.delenv("PFML_QUAD_DIRECT", raising=False)
+    monkeypatch.delenv("PFML_QUAD_MM", raising=False)
+    pipe = quadform_utilities(*args).cpu()
     monkeypatch.setenv("PFML_QUAD_DIRECT", "1")
     direct = quadform_utilities(*args).cpu()
+    assert torch.equal(pipe, direct)
+    ref = quadform_utilities(D, R, beta, jc, jm, jn)
+    assert torch.allclose(pipe, ref, rtol=1e-11, atol=1e-11)
     assert torch.allclose(direct, ref, rtol=1e-11, atol=1e-11)
 
 
-@pytest.mark.parametrize("direct", ["0", "1"])
+@pytest.mark.parametrize("direct", [None, "1"], ids=["default", "1"])
 def test_quadform_production_shape(gpu, monkeypatch, direct):
     """Both utilities forms at the production cell size (n = 513: nine row tiles, tail index
     split off) and a mixed launch (n = 257 / 129 / 65 cells), against the CPU oracle."""
     from pfml.ops.ridge import quadform_utilities
-    monkeypatch.setenv("PFML_QUAD_DIRECT", direct)
+    if direct is None:
+        monkeypatch.delenv("PFML_QUAD_DIRECT", raising=False)
+    else:
+        monkeypatch.setenv("PFML_QUAD_DIRECT", direct)
     P, L = 513, 101
     D = _spd_stack(4, P, n_obs=600, seed=98) / 600
     R = _rand(4, P, seed=99)
