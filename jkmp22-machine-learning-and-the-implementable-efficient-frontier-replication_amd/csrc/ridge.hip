@@ -28,6 +28,7 @@
 //   (ridge_backtransform_wy_kernel; measured 12-34x faster than the one-at-a-time form at
 //   n = 1025 and 2049, profiles/r08_large_p.json).
 #include "common.h"
+#include "ridge_band.h"
 #include "ridge_desc.h"
 #include <cstdlib>
 
@@ -55,6 +56,28 @@ typedef RidgeCellDesc CellDesc;
 // (VW[i][0..PB) = V, VW[i][PB..2PB) = W) so correction dots are coalesced.
 constexpr int PB = 16;
 
+// Per-cell workspace layout of this path (doubles).  P: double* in the kernels (the regions'
+// addresses); int64_t on the host (offsets from the cell's base: `end` is the size).
+template <class P>
+struct TriWorkT {
+  P A, Y, Ua, Ub, Uc, Uy, d, e, tau, z, VW, end;
+  __host__ __device__ TriWorkT(P w, int n, int L) {
+    A = w;                                   // n x n working matrix; reflector k in row k
+    Y = A + (int64_t)n * n;                  // n x L solutions y_l of the tridiagonal systems
+    Ua = Y + (int64_t)n * L;                 // n x L each: the pivoted elimination's three
+    Ub = Ua + (int64_t)n * L;                //   upper diagonals
+    Uc = Ub + (int64_t)n * L;
+    Uy = Uc + (int64_t)n * L;                //   and its right-hand side
+    d = Uy + (int64_t)n * L;                 // diagonal of T
+    e = d + n;                               // sub-diagonal of T
+    tau = e + n;                             // reflector scalars
+    z = e + 2 * n;                           // Q^T rbar, behind tau
+    VW = z + n;                              // [n][2 PB] panel reflectors V and updates W
+    end = VW + (int64_t)n * 2 * PB;
+  }
+};
+typedef TriWorkT<double*> TriWork;
+
 template <int CAP>
 __global__ __launch_bounds__(NT) void ridge_tridiag_blocked_kernel(
     const double* __restrict__ SD, int64_t ldS, const double* __restrict__ Sr,
@@ -70,14 +93,13 @@ __global__ __launch_bounds__(NT) void ridge_tridiag_blocked_kernel(
   const int n = cd.n;
   const int t = threadIdx.x, lane = t & 63;
   const int wid = __builtin_amdgcn_readfirstlane(t >> 6);
-  double* A = work + cd.work;
-  double* Y = A + (int64_t)n * n;
-  double* Uy = Y + 4LL * n * L;
-  double* dg = Uy + (int64_t)n * L;
-  double* eg = dg + n;
-  double* tg = eg + n;
-  double* zg = tg + n;
-  double* VW = zg + n;                         // [n][2*PB]
+  const TriWork tw(work + cd.work, n, L);
+  double* A = tw.A;
+  double* dg = tw.d;
+  double* eg = tw.e;
+  double* tg = tw.tau;
+  double* zg = tw.z;
+  double* VW = tw.VW;
   const double* S = SD + cd.src;
   const double sc = cd.scale;
 
@@ -295,15 +317,15 @@ __global__ __launch_bounds__(256) void ridge_trisolve_kernel(
   const int cell = (int)(gid / L), l = (int)(gid % L);
   const CellDesc cd = cells[cell];
   const int n = cd.n;
-  double* A = work + cd.work;
-  double* Y = A + (int64_t)n * n;
-  double* Ua = Y + (int64_t)n * L;
-  double* Ub = Ua + (int64_t)n * L;
-  double* Uc = Ub + (int64_t)n * L;
-  double* Uy = Uc + (int64_t)n * L;
-  const double* dd = Uy + (int64_t)n * L;
-  const double* ee = dd + n;
-  const double* z = ee + 2 * n;
+  const TriWork tw(work + cd.work, n, L);
+  double* Y = tw.Y;
+  double* Ua = tw.Ua;
+  double* Ub = tw.Ub;
+  double* Uc = tw.Uc;
+  double* Uy = tw.Uy;
+  const double* dd = tw.d;
+  const double* ee = tw.e;
+  const double* z = tw.z;
   const double lam = lvec[l];
   double a = dd[0] + lam, b = (n > 1) ? ee[0] : 0.0, c = 0.0, y = z[0];
   for (int i = 0; i + 1 < n; ++i) {
@@ -364,9 +386,10 @@ __global__ __launch_bounds__(NT) void ridge_backtransform_kernel(
     if (n > n_skip) return;
   const int t = threadIdx.x, lane = t & 63;
   const int wid = __builtin_amdgcn_readfirstlane(t >> 6);   // wave-uniform row part
-  double* A = work + cd.work;
-  double* Y = A + (int64_t)n * n;
-  const double* tg = Y + 5LL * n * L + 2 * n;
+  const TriWork tw(work + cd.work, n, L);
+  double* A = tw.A;
+  double* Y = tw.Y;
+  const double* tg = tw.tau;
   for (int i = t; i < n; i += NT) tau[i] = tg[i];
   __syncthreads();
   // ================================ Phase C ============================================
@@ -524,9 +547,10 @@ __global__ __launch_bounds__(NT) void ridge_backtransform_wy_kernel(
   const int t = threadIdx.x, lane = t & 63;
   const int wid = __builtin_amdgcn_readfirstlane(t >> 6);
   const int c16 = lane & 15, g4 = lane >> 4;
-  const double* A = work + cd.work;
-  const double* Y = A + (int64_t)n * n;
-  const double* tg = Y + 5LL * n * L + 2 * n;
+  const TriWork tw(work + cd.work, n, L);
+  const double* A = tw.A;
+  const double* Y = tw.Y;
+  const double* tg = tw.tau;
   double* out = beta_out + cd.out;
   const int l0 = chunk * WLC;
   const int l = l0 + c16;
@@ -644,89 +668,62 @@ __global__ __launch_bounds__(NT) void ridge_backtransform_wy_kernel(
 
 }  // namespace
 
-extern "C" int64_t pfml_ridge_band_work_doubles(int n, int L);
-extern "C" int pfml_ridge_band_nmax();
-extern "C" hipError_t pfml_ridge_band_launch(const double* SD, int64_t ldS, const double* Sr,
-                                             const void* cells, int ncells, const double* lvec,
-                                             int L, double* work, double* beta_out, int64_t ldo,
-                                             long long* tim, int* lu_list, int* lu_count,
-                                             int lu_cap, const int* wgmap, int nwg,
-                                             unsigned* syncw, const int* n_host,
-                                             hipStream_t st);
-
-// Workspace per cell: enough for whichever path the launcher picks (band path: ridge_band.hip).
+// Workspace per cell: enough for whichever path the launcher picks (band path: ridge_band.h).
 extern "C" int64_t pfml_ridge_work_doubles(int n, int L) {
-  const int64_t tri = (int64_t)n * n + 5LL * n * L + 4LL * n + 32LL * n;
+  const int64_t tri = TriWorkT<int64_t>(0, n, L).end;
   const int64_t band = pfml_ridge_band_work_doubles(n, L);
   // rounded to 32 doubles: every cell's workspace (and so its band matrix, whose rows the
   // band kernels store 16 bytes at a time) starts 256-byte aligned
   return ((tri > band ? tri : band) + 31) / 32 * 32;
 }
 
-static long long* g_ridge_timing = nullptr;
-// Debug: per-cell phase cycle counters of the band reduction (tools/bench_ridge.py --timing).
-extern "C" void pfml_ridge_set_timing(long long* buf) { g_ridge_timing = buf; }
-
-static int g_bt_wy = 1;
-// A/B switch of the back-transform of cells with n > 1024 for later launches: 1 (default) the
-// blocked MFMA kernel, 0 the one-reflector-at-a-time generic path (tools/bench_large_p.py).
-extern "C" void pfml_ridge_set_bt_wy(int on) { g_bt_wy = on ? 1 : 0; }
-
-static int g_phases = 7;
-// Debug: phases of the tridiagonal path that later launches queue (bit 0 tridiagonalisation,
-// bit 1 tridiagonal solves, bit 2 back-transform; default all).  tools/bench_large_p.py times
-// one phase at a time between event pairs; a launch with phases left out computes nothing
-// useful.
-extern "C" void pfml_ridge_set_phases(int mask) { g_phases = mask & 7; }
-
 // n <= 528: the band path (ridge_band.hip: cooperative reduction, banded Cholesky, in-band
 // pivoted-LU repair of non-SPD lambdas through lu_list / lu_count / lu_cap, nullptr = off);
 // 528 < n <= 2049: the blocked tridiagonal path below (the CAP_S instances for a launch with
 // nmax <= 1024, else CAP_L), whose NaN markers go to the dense repair (ridge_repair.hip).
-extern "C" hipError_t pfml_ridge_grid(const double* SD, int64_t ldS, const double* Sr,
-                                      const void* cells, int ncells, int nmax,
-                                      const double* lvec, int L, double* work, double* beta_out,
-                                      int64_t ldo, int* lu_list, int* lu_count, int lu_cap,
-                                      const int* wgmap, int nwg, unsigned* syncw,
-                                      const int* n_host, hipStream_t st) {
-  if (ncells <= 0) return hipSuccess;
-  if (L > 128 || nmax > NMAX) return hipErrorInvalidValue;
-  const CellDesc* cd = static_cast<const CellDesc*>(cells);
-  if (nmax <= pfml_ridge_band_nmax())
-    return pfml_ridge_band_launch(SD, ldS, Sr, cells, ncells, lvec, L, work, beta_out, ldo,
-                                  g_ridge_timing, lu_list, lu_count, lu_cap, wgmap, nwg, syncw,
-                                  n_host, st);
-  const bool large = nmax > CAP_S;
-  if (!(g_phases & 1)) {
+// The launch is `a` and nothing else: no option outlives the call.  A launch with phases
+// left out (a.phases != 7: tools/bench_large_p.py times one phase between event pairs)
+// computes nothing useful unless `work` holds the earlier phases of a full launch.
+extern "C" hipError_t pfml_ridge_grid(const RidgeLaunchArgs* a, hipStream_t st) {
+  if (a == nullptr) return hipErrorInvalidValue;
+  if (a->ncells <= 0) return hipSuccess;
+  if (a->L > 128 || a->nmax > NMAX) return hipErrorInvalidValue;
+  if (a->nmax <= pfml_ridge_band_nmax()) return ridge_band_launch(*a, st);
+  const CellDesc* cd = a->cells;
+  const int ncells = a->ncells, L = a->L;
+  const bool large = a->nmax > CAP_S;
+  if (!(a->phases & 1)) {
   } else if (large)
-    hipLaunchKernelGGL(ridge_tridiag_blocked_kernel<CAP_L>, dim3(ncells), dim3(NT), 0, st, SD,
-                       ldS, Sr, cd, L, work);
+    hipLaunchKernelGGL(ridge_tridiag_blocked_kernel<CAP_L>, dim3(ncells), dim3(NT), 0, st, a->SD,
+                       a->ldS, a->Sr, cd, L, a->work);
   else
-    hipLaunchKernelGGL(ridge_tridiag_blocked_kernel<CAP_S>, dim3(ncells), dim3(NT), 0, st, SD,
-                       ldS, Sr, cd, L, work);
+    hipLaunchKernelGGL(ridge_tridiag_blocked_kernel<CAP_S>, dim3(ncells), dim3(NT), 0, st, a->SD,
+                       a->ldS, a->Sr, cd, L, a->work);
   const int64_t nth = (int64_t)ncells * L;
-  if (g_phases & 2)
+  if (a->phases & 2)
     hipLaunchKernelGGL(ridge_trisolve_kernel, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0,
-                       st, cd, ncells, lvec, L, work);
-  if (!(g_phases & 4)) {
+                       st, cd, ncells, a->lvec, L, a->work);
+  if (!(a->phases & 4)) {
   } else if (large) {
     // cells with n > 1024 on the blocked back-transform (one workgroup per 16 lambdas), the
     // launch's smaller cells on the kernel they have in a small launch; each kernel's
-    // workgroups leave the other's cells at once
-    const int n_skip = g_bt_wy ? CAP_S : NMAX;
+    // workgroups leave the other's cells at once.  bt_wy off (the A/B arm): the
+    // one-reflector-at-a-time generic path for all.
+    const int n_skip = a->bt_wy ? CAP_S : NMAX;
     hipLaunchKernelGGL(ridge_backtransform_kernel<CAP_L>, dim3(ncells), dim3(NT), 0, st, cd, L,
-                       work, beta_out, ldo, n_skip);
-    if (g_bt_wy) {
+                       a->work, a->beta, a->ldo, n_skip);
+    if (a->bt_wy) {
       const int nchunk = (L + WLC - 1) / WLC;
       hipLaunchKernelGGL(ridge_backtransform_wy_kernel<CAP_L>, dim3(ncells * nchunk), dim3(NT),
-                         0, st, cd, L, nchunk, n_skip, work, beta_out, ldo);
+                         0, st, cd, L, nchunk, n_skip, a->work, a->beta, a->ldo);
     }
   } else {
     hipLaunchKernelGGL(ridge_backtransform_kernel<CAP_S>, dim3(ncells), dim3(NT), 0, st, cd, L,
-                       work, beta_out, ldo, NMAX);
+                       a->work, a->beta, a->ldo, NMAX);
   }
   return hipGetLastError();
 }
 
 extern "C" int pfml_ridge_cell_desc_size() { return (int)sizeof(CellDesc); }
+extern "C" int pfml_ridge_launch_args_size() { return (int)sizeof(RidgeLaunchArgs); }
 extern "C" int pfml_ridge_nmax() { return NMAX; }

@@ -28,8 +28,6 @@ def _declare_hip(lib):
     P, I, L, D = C.c_void_p, C.c_int, C.c_int64, C.c_double
     lib.pfml_dgemm.argtypes = [I, I, I, I, I, I, D, P, L, L, P, L, L, D, P, L, L, P, L, P, L, P]
     lib.pfml_dgemm.restype = I
-    lib.pfml_ridge_grid.argtypes = [P, L, P, P, I, I, P, I, P, P, L, P, P, I, P, I, P, P, P]
-    lib.pfml_ridge_grid.restype = I
     lib.pfml_ridge_work_doubles.argtypes = [I, I]
     lib.pfml_ridge_work_doubles.restype = L
     lib.pfml_ridge_cell_desc_size.restype = I
@@ -53,8 +51,6 @@ def _declare_hip(lib):
     lib.pfml_lu_solve_work_doubles.argtypes = [I, I, I]
     lib.pfml_lu_solve_work_doubles.restype = L
     lib.pfml_lu_solve_max_n.restype = I
-    lib.pfml_ridge_set_timing.argtypes = [P]
-    lib.pfml_ridge_set_timing.restype = None
     for name, argt in _EXTRA_HIP.items():
         fn = getattr(lib, name)
         fn.argtypes = argt[0]

@@ -21,6 +21,20 @@ JOB_DTYPE = np.dtype([("d_off", "<i8"), ("r_off", "<i8"), ("b_off", "<i8"), ("o_
                       ("n", "<i4"), ("ptile0", "<i4")])
 
 
+class LaunchArgs(C.Structure):
+    """csrc/ridge_desc.h RidgeLaunchArgs: one ridge-grid launch, options included."""
+    _P, _I, _L, _B = C.c_void_p, C.c_int, C.c_int64, C.c_bool
+    _fields_ = [("SD", _P), ("ldS", _L), ("Sr", _P), ("cells", _P), ("ncells", _I), ("nmax", _I),
+                ("lvec", _P), ("L", _I), ("work", _P), ("beta", _P), ("ldo", _L),
+                ("lu_list", _P), ("lu_count", _P), ("lu_cap", _I), ("wgmap", _P), ("nwg", _I),
+                ("syncw", _P), ("n_host", _P), ("timing", _P), ("spin_max", C.c_uint),
+                ("phases", _I), ("solo", _B), ("bt_wy", _B), ("bt_classes", _B)]
+
+
+nat.register_hip("pfml_ridge_grid", [C.POINTER(LaunchArgs), C.c_void_p])
+nat.register_hip("pfml_ridge_timing_words", [C.c_int], C.c_int64)
+
+
 def segment_sums(X: torch.Tensor, starts, stops, dev_bounds=None) -> torch.Tensor:
     """out[s] = X[starts[s]:stops[s]].sum(0) for X of shape [T, ...].  ``dev_bounds``:
     device int32 copies of (starts, stops), e.g. from a cached plan (no host->device copy)."""
@@ -287,7 +301,7 @@ def _work_doubles(n_arr: np.ndarray, L: int) -> np.ndarray:
 
 
 COOP_KMAX = 16          # workgroups per cell of the cooperative band reduction (wgmap: 4 bits)
-COOP_SYNC_WORDS = 32    # csrc/ridge_band.hip COOP_SYNC: int32 sync words per cell
+COOP_SYNC_WORDS = 32    # csrc/ridge_band.h COOP_SYNC (pfml_coop_sync_words): int32 sync words per cell
 COOP_BIG_SHARE = 0.42   # share of the CUs the largest cells' cooperative launch gets (coop_k)
 QUAD_DIRECT, QUAD_PIPE, QUAD_PIPE_REST = 3, 4, 5     # csrc/quadform.hip pfml_quadform's `form`
 
@@ -296,6 +310,8 @@ QUAD_DIRECT, QUAD_PIPE, QUAD_PIPE_REST = 3, 4, 5     # csrc/quadform.hip pfml_qu
 class Switches:
     """Every environment variable that shapes a grid-step launch, read in one place
     (``switches()``): per field the default, and the variable that selects the other A/B arm.
+    The library keeps no state: the fields it acts on travel with every launch
+    (``launch_opts`` -> ``LaunchArgs``), the rest shape the host-side plans.
 
     coop_k         ``coop_k``'s policy; PFML_COOP_K=k (not empty): k workgroups per largest cell
     coop_solo      a launch whose cells all have K = 1 on the solo kernel; PFML_COOP_SOLO=0: not
@@ -413,6 +429,10 @@ def ridge_plan(P: int, L: int, cell_src, cell_n, cell_scale, ncu: int = 256,
     lib = nat.hip_lib()
     if lib.pfml_ridge_cell_desc_size() != CELL_DTYPE.itemsize:
         raise RuntimeError("CellDesc layout mismatch between python and libpfml_hip")
+    if lib.pfml_ridge_launch_args_size() != C.sizeof(LaunchArgs):
+        raise RuntimeError("RidgeLaunchArgs layout mismatch between python and libpfml_hip")
+    if lib.pfml_coop_sync_words() != COOP_SYNC_WORDS:
+        raise RuntimeError("COOP_SYNC_WORDS differs from libpfml_hip's sync words per cell")
     nc = len(cell_src)
     cell_n = np.asarray(cell_n)
     nlim = int(lib.pfml_ridge_nmax())
@@ -493,45 +513,67 @@ def band_path(plan: dict) -> bool:
     return plan["nmax"] <= nat.hip_lib().pfml_ridge_band_nmax()
 
 
+def launch_opts(sw: Switches, spin_override: int | None = None) -> dict:
+    """The option fields of ``LaunchArgs`` that the switches set.  ``spin_override``: the
+    ``set_coop_spin_max`` value (None: the module's current one); non-zero, it wins over
+    ``sw.coop_spin_max``.  0 means the library's default bound."""
+    if spin_override is None:
+        spin_override = _SPIN_OVERRIDE[0]
+    return {"spin_max": int(spin_override or sw.coop_spin_max), "solo": bool(sw.coop_solo),
+            "bt_wy": bool(sw.bt_wy), "bt_classes": bool(sw.bt_classes)}
+
+
 def ridge_launch(plan: dict, d_desc: torch.Tensor, SD: torch.Tensor, Sr: torch.Tensor,
                  lv: torch.Tensor, beta: torch.Tensor, repair: bool = True,
                  d_wgmap: torch.Tensor | None = None,
-                 sw: Switches | None = None) -> torch.Tensor | None:
+                 sw: Switches | None = None, *, timing: torch.Tensor | None = None,
+                 phases: int = 7, work: torch.Tensor | None = None) -> torch.Tensor | None:
     """Queue one ridge-grid launch; returns the device count of non-SPD systems re-solved by
-    the band path's pivoted banded LU (kernel 2b of ridge_band.hip), None when the launch has
-    no in-band repair (``repair=False`` or the tridiagonal path).  ``d_wgmap``: the device
-    copy of plan["wgmap"] (the cooperative band reduction's workgroup map)."""
+    the band path's pivoted banded LU (kernel 2b, ridge_band_solve.hip), None when the launch
+    has no in-band repair (``repair=False`` or the tridiagonal path).  ``d_wgmap``: the device
+    copy of plan["wgmap"] (the cooperative band reduction's workgroup map).  For this launch
+    only: ``timing``, an int64 device buffer of pfml_ridge_timing_words(cells) words for the
+    band path's cycle counters; ``phases``, the tridiagonal path's phases to queue (bit 0
+    tridiagonalisation, 1 solves, 2 back-transform), which read the earlier phases from
+    ``work`` (plan["work"] doubles, default a fresh one): that of a preceding full launch."""
     sw = sw or switches()
+    lib = nat.hip_lib()
     P = SD.shape[-1]
     L = int(lv.numel())
-    work = torch.empty(plan["work"], dtype=torch.float64, device=SD.device)
-    count = lst = None
+    nc = plan["nc"]
     band = band_path(plan)
-    if repair and band:
-        count = torch.empty(1, dtype=torch.int32, device=SD.device)   # zeroed by the solve
-        lst = torch.empty(plan["nc"] * L, dtype=torch.int32, device=SD.device)
+    if phases != 7 and (work is None or band):
+        raise ValueError("ridge_launch: a launch with phases left out needs the work tensor of "
+                         "a preceding full launch (tridiagonal path only)")
     if band and d_wgmap is None:
         raise ValueError("ridge_launch: the cooperative reduction needs the device wgmap")
-    _apply_switches(sw, band)
-    sync = (torch.empty(plan["nc"] * COOP_SYNC_WORDS, dtype=torch.int32, device=SD.device)
-            if band else None)
+    if work is None:
+        work = torch.empty(plan["work"], dtype=torch.float64, device=SD.device)
+    elif work.dtype != torch.float64 or work.device != SD.device or work.numel() < plan["work"]:
+        raise ValueError(f"ridge_launch: work must hold {plan['work']} doubles on {SD.device}")
+    if timing is not None:
+        tw = lib.pfml_ridge_timing_words(nc)
+        if timing.dtype != torch.int64 or timing.device != SD.device or timing.numel() < tw:
+            raise ValueError(f"ridge_launch: timing must hold {tw} int64 words on {SD.device}")
+    args = LaunchArgs(SD=SD.data_ptr(), ldS=P, Sr=Sr.data_ptr(), cells=d_desc.data_ptr(),
+                      ncells=nc, nmax=plan["nmax"], lvec=lv.data_ptr(), L=L,
+                      work=work.data_ptr(), beta=beta.data_ptr(), ldo=beta.shape[-1],
+                      lu_cap=nc * L,
+                      # host pointer to the plan's per-cell n (read during the launch call only)
+                      n_host=plan["n_host"].ctypes.data, timing=nat.ptr(timing),
+                      phases=phases, **launch_opts(sw))
+    count = None
     if band:
+        if repair:
+            count = torch.empty(1, dtype=torch.int32, device=SD.device)   # zeroed by the solve
+            lst = torch.empty(nc * L, dtype=torch.int32, device=SD.device)
+            args.lu_list, args.lu_count = lst.data_ptr(), count.data_ptr()
+        sync = torch.empty(nc * COOP_SYNC_WORDS, dtype=torch.int32, device=SD.device)
         # every launch's sync words are kept until the next grid search starts (the big and the
         # small cells' launches run on two streams: neither may hide the other's timeouts)
         LAST_COOP_SYNC.append(sync)
-    # host pointer to the plan's per-cell n (read during the launch call only)
-    n_host = plan["n_host"].ctypes.data if sw.bt_classes else None
-    nat.check(nat.hip_lib().pfml_ridge_grid(SD.data_ptr(), P, Sr.data_ptr(), d_desc.data_ptr(),
-                                            plan["nc"], plan["nmax"], lv.data_ptr(), L,
-                                            work.data_ptr(), beta.data_ptr(), beta.shape[-1],
-                                            lst.data_ptr() if lst is not None else None,
-                                            count.data_ptr() if count is not None else None,
-                                            plan["nc"] * L,
-                                            d_wgmap.data_ptr() if band else None,
-                                            len(plan["wgmap"]) if band else 0,
-                                            sync.data_ptr() if band else None,
-                                            n_host, nat.stream_of(SD)),
-              "pfml_ridge_grid")
+        args.wgmap, args.nwg, args.syncw = d_wgmap.data_ptr(), len(plan["wgmap"]), sync.data_ptr()
+    nat.check(lib.pfml_ridge_grid(C.byref(args), nat.stream_of(SD)), "pfml_ridge_grid")
     return count
 
 
@@ -539,7 +581,6 @@ def ridge_launch(plan: dict, d_desc: torch.Tensor, SD: torch.Tensor, Sr: torch.T
 # the error word is index 1 of every cell's COOP_SYNC_WORDS): a timed-out cell's betas are NaN
 # (the back-transform poisons them) and the grid search's non-finite recovery recomputes them
 LAST_COOP_SYNC: list = []
-nat.register_hip("pfml_coop_set_spin_max", [C.c_uint], None)
 
 
 def reset_coop_sync() -> None:
@@ -562,16 +603,6 @@ def set_coop_spin_max(n: int) -> None:
     """Poll bound of the cooperative reduction's waits for later launches (tests lower it to
     force timeouts); it wins over ``PFML_COOP_SPIN_MAX`` until it is called with 0."""
     _SPIN_OVERRIDE[0] = int(n)
-
-
-def _apply_switches(sw: Switches, band: bool) -> None:
-    """Set the switches the library keeps as host globals, read by the next launch call."""
-    lib = nat.hip_lib()
-    if band:
-        lib.pfml_coop_set_spin_max(_SPIN_OVERRIDE[0] or sw.coop_spin_max)
-        lib.pfml_coop_set_solo(int(sw.coop_solo))
-    else:
-        lib.pfml_ridge_set_bt_wy(int(sw.bt_wy))
 
 
 def ridge_grid(SD: torch.Tensor, Sr: torch.Tensor, cell_src: np.ndarray, cell_n: np.ndarray,

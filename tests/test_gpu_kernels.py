@@ -622,7 +622,7 @@ def test_ridge_utilities_stream_groups(gpu, streams, monkeypatch):
 
 def test_backtransform_size_classes(gpu, monkeypatch):
     """The back-transform's size-class instances (2 / 4 / 4 / 8 waves for n <= 96 / 192 / 320
-    / 528, csrc/ridge_band.hip ridge_band_bt_launch) against the single 8-wave form
+    / 528, csrc/ridge_band_bt.hip band_bt_launch) against the single 8-wave form
     (PFML_BT_CLASSES=0) on a launch mixing all four classes: the same betas to rounding (the
     partial sums of V'Y run over a different wave split), and both against the CPU oracle."""
     from pfml.ops import ridge as rg

@@ -21,6 +21,7 @@
 Each mode merges its section into ``--out`` (default profiles/r08_large_p.json).
 """
 import argparse
+import dataclasses
 import json
 import os
 import subprocess
@@ -64,7 +65,6 @@ def kernel_split(reals, cfg) -> dict:
     """One eager grid step's ridge / repair / utilities launches, group by group between event
     pairs on one stream (sums over the groups, ms)."""
     from pfml.models.search import _search_setup, window_sums
-    from pfml.ops import _native as nat
     from pfml.ops import ridge as rg
     dev = reals.denom.device
     G, T, P = reals.G, reals.denom.shape[1], reals.P
@@ -81,7 +81,6 @@ def kernel_split(reals, cfg) -> dict:
                               su["jc"], su["jm"], su["jn"], split=True)
     beta = torch.empty((len(su["cell_n"]), L, P), dtype=torch.float64, device=dev)
     obj = torch.empty((len(su["jc"]), L), dtype=torch.float64, device=dev)
-    lib = nat.hip_lib()
     out = {"band_launch": 0.0, "tridiagonalisation": 0.0, "tridiagonal_solves": 0.0,
            "back_transform": 0.0, "repair": 0.0, "utilities": 0.0, "groups": []}
     dv = plan["dv"]
@@ -93,17 +92,16 @@ def kernel_split(reals, cfg) -> dict:
                 lambda: rg.ridge_launch(rp, d_desc, SD, Sr, lv, beta, d_wgmap=d_wg))
             out["band_launch"] += rec["band_launch"]
         else:
-            rg.ridge_launch(rp, d_desc, SD, Sr, lv, beta, d_wgmap=d_wg)     # valid workspace
+            # one workspace for the full launch and the single phases that read its results
+            work = torch.empty(rp["work"], dtype=torch.float64, device=dev)
+            rg.ridge_launch(rp, d_desc, SD, Sr, lv, beta, d_wgmap=d_wg, work=work)
             for bit, name in ((1, "tridiagonalisation"), (2, "tridiagonal_solves"),
                               (4, "back_transform")):
-                lib.pfml_ridge_set_phases(bit)
-                try:
-                    rec[name] = _event_ms(
-                        lambda: rg.ridge_launch(rp, d_desc, SD, Sr, lv, beta, d_wgmap=d_wg))
-                finally:
-                    lib.pfml_ridge_set_phases(7)
+                rec[name] = _event_ms(
+                    lambda: rg.ridge_launch(rp, d_desc, SD, Sr, lv, beta, d_wgmap=d_wg,
+                                            phases=bit, work=work))
                 out[name] += rec[name]
-            rg.ridge_launch(rp, d_desc, SD, Sr, lv, beta, d_wgmap=d_wg)     # betas for (utilities)
+            rg.ridge_launch(rp, d_desc, SD, Sr, lv, beta, d_wgmap=d_wg, work=work)  # betas for (utilities)
             rec["repair"] = _event_ms(lambda: rg.repair_launch(rp, d_desc, SD, Sr, lv, beta))
             out["repair"] += rec["repair"]
         rec["utilities"] = _event_ms(lambda: rg.quad_launch(qp, d_q, d_tj, D, R, beta, obj))
@@ -162,10 +160,8 @@ def _load(path: str) -> dict:
 
 
 def mode_ab(args) -> None:
-    from pfml.ops import _native as nat
     from pfml.ops import ridge as rg
     dev = torch.device("cuda", 0)
-    lib = nat.hip_lib()
     lv = torch.tensor([0.0] + list(np.exp(np.linspace(-10, 10, 100))), dtype=torch.float64,
                       device=dev)
     L = int(lv.numel())
@@ -181,23 +177,22 @@ def mode_ab(args) -> None:
             plan = rg.ridge_plan(n, L, src, nn, sc)
             d_desc, = rg.upload([plan["desc"]], dev)
             beta = torch.empty((ncells, L, n), dtype=torch.float64, device=dev)
-            launch = lambda: rg.ridge_launch(plan, d_desc, SD, Sr, lv, beta)   # noqa: E731
-            arms = {"blocked_mfma": "1", "generic": "0"}
+            work = torch.empty(plan["work"], dtype=torch.float64, device=dev)
+            arms = {"blocked_mfma": dataclasses.replace(rg.switches(), bt_wy=True),
+                    "generic": dataclasses.replace(rg.switches(), bt_wy=False)}
+
+            def launch(k, phases=7):
+                rg.ridge_launch(plan, d_desc, SD, Sr, lv, beta, sw=arms[k], phases=phases,
+                                work=work)
+
             betas, ts, whole = {}, {k: [] for k in arms}, {}
-            try:
-                for k, v in arms.items():                 # whole launch, and the betas to compare
-                    os.environ["PFML_RIDGE_BT_WY"] = v
-                    launch()
-                    whole[k] = _event_ms(launch)
-                    betas[k] = beta.clone()
-                for _ in range(args.reps):                # back-transform alone, arms alternating
-                    for k, v in arms.items():
-                        os.environ["PFML_RIDGE_BT_WY"] = v
-                        lib.pfml_ridge_set_phases(4)
-                        ts[k].append(_event_ms(launch))
-            finally:
-                lib.pfml_ridge_set_phases(7)
-                os.environ.pop("PFML_RIDGE_BT_WY", None)
+            for k in arms:                            # whole launch, and the betas to compare
+                launch(k)
+                whole[k] = _event_ms(lambda: launch(k))
+                betas[k] = beta.clone()
+            for _ in range(args.reps):                # back-transform alone, arms alternating
+                for k in arms:
+                    ts[k].append(_event_ms(lambda: launch(k, phases=4)))
             dif = ((betas["blocked_mfma"] - betas["generic"]).norm(dim=-1)
                    / betas["generic"].norm(dim=-1)).max().item()
             rec = {"n": n, "cells": ncells, "L": L, "reps": args.reps,

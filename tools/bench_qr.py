@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Panel-QR micro-benchmark: band_panel_hh (csrc/ridge_band.hip) in isolation.
+"""Panel-QR micro-benchmark: band_panel_hh (csrc/ridge_band_reduce.hip) in isolation.
 
 Cycles per m x 16 panel factorisation (the band reduction's serial step, once per panel on
 the critical chain of every ridge cell), column-by-column Householder with the panel in LDS,

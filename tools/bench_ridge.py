@@ -40,13 +40,25 @@ def timing(n=513):
     """Per-phase cycle split of the cooperative band reduction: 8 phase slots for workgroup 0
     (the QR one) and 1 of cell 0, plus the banded solve's forward / backward cycles."""
     from pfml.ops import _native as nat
+    from pfml.ops import ridge as rg
     dev = torch.device("cuda", 0)
     ncells = int(os.environ.get("PFML_TIMING_CELLS", "1"))
-    buf = torch.zeros(ncells * 16 + 16, dtype=torch.int64, device=dev)
-    nat.hip_lib().pfml_ridge_set_timing(buf.data_ptr())
-    run(ncells, n, reps=1)
+    P = 513
+    S = max(1, ncells // 4)
+    X = torch.randn(S, 600, P, dtype=torch.float64, device=dev)
+    SD = X.transpose(1, 2) @ X
+    Sr = torch.randn(S, P, dtype=torch.float64, device=dev)
+    lv = torch.tensor([0.0] + list(np.exp(np.linspace(-10, 10, 100))), dtype=torch.float64,
+                      device=dev)
+    plan = rg.ridge_plan(P, int(lv.numel()), np.arange(ncells) % S, np.full(ncells, n),
+                         np.full(ncells, 1e-3), ncu=rg.num_cus(dev))
+    d_desc, d_wg = rg.upload([plan["desc"], plan["wgmap"]], dev)
+    beta = torch.empty((ncells, int(lv.numel()), P), dtype=torch.float64, device=dev)
+    words = int(nat.hip_lib().pfml_ridge_timing_words(ncells))
+    buf = torch.zeros(words, dtype=torch.int64, device=dev)
+    for tim in (None, buf):                      # one untimed launch first, as a warm-up
+        rg.ridge_launch(plan, d_desc, SD, Sr, lv, beta, d_wgmap=d_wg, timing=tim)
     torch.cuda.synchronize()
-    nat.hip_lib().pfml_ridge_set_timing(None)
     allb = buf.cpu().numpy()
     names = ["init_panel0", "U", "X_partials", "sync_wait", "C_sums_W", "update",
              "lookahead_qr", "end_sync"]
@@ -56,8 +68,8 @@ def timing(n=513):
         tot = max(1, int(t.sum()))
         out[f"wg{w}"] = {nm: f"{int(v)} cyc ({100.0 * v / tot:.1f}%)" for nm, v in zip(names, t)}
         out[f"wg{w}_total_cyc"] = tot
-    out.update({"solve_fwd_cyc": int(allb[ncells * 16]),
-                "solve_bwd_cyc": int(allb[ncells * 16 + 1])})
+    # (the solve kernel's slots are the last 16 words, behind the cells')
+    out.update({"solve_fwd_cyc": int(allb[words - 16]), "solve_bwd_cyc": int(allb[words - 15])})
     return out
 
 
