@@ -55,6 +55,34 @@ def _opt_hps(validation: pd.DataFrame, g: int) -> pd.DataFrame:
                          "l": sel["l"].to_numpy(), "p": sel["p"].to_numpy()})
 
 
+def _aim_gemv(sig: list, coefs: torch.Tensor, nk, offs, out: torch.Tensor) -> torch.Tensor:
+    """out[offs[j] + r] = sig[j][r, :nk[j]] . coefs[j, :nk[j]] for every row r of every job j in
+    ONE launch (csrc/weights.hip aim_gemv_kernel).  sig[j]: a device [nrow_j, >= nk_j] fp64
+    view with unit inner stride, read in place; coefs: [J, >= max nk] row-major; out: a
+    contiguous fp64 buffer, touched only at the jobs' rows."""
+    from ..ops.ridge import upload
+    J = len(sig)
+    if J == 0:
+        return out
+    if nat.hip_lib().pfml_aim_job_size() != AIM_JOB.itemsize:
+        raise RuntimeError("AimJob layout mismatch between python and libpfml_hip")
+    if not out.is_contiguous() or coefs.stride(-1) != 1 or \
+            any(x.stride(-1) != 1 for x in sig):
+        raise ValueError("_aim_gemv: unsupported layout")
+    nrows = np.asarray([int(x.shape[0]) for x in sig], np.int64)
+    jobs = np.zeros(J, AIM_JOB)
+    jobs["s"] = [x.data_ptr() for x in sig]
+    jobs["ld"] = [x.stride(0) for x in sig]
+    jobs["off"] = np.asarray(offs, np.int64)
+    jobs["nrow"] = nrows
+    jobs["nk"] = np.asarray(nk, np.int64)
+    (dj,) = upload([jobs], out.device)
+    nat.check(nat.hip_lib().pfml_aim_gemv(dj.data_ptr(), J, int(nrows.max()), coefs.data_ptr(),
+                                          coefs.stride(0), out.data_ptr(), nat.stream_of(out)),
+              "pfml_aim_gemv")
+    return out
+
+
 def aim_portfolios(cfg: Config, validation: pd.DataFrame, beta_years: np.ndarray,
                    beta: torch.Tensor, signal_months: np.ndarray, signal_t: list,
                    signal_ids: list, oos_months: np.ndarray) -> dict:
@@ -93,21 +121,8 @@ def aim_portfolios(cfg: Config, validation: pd.DataFrame, beta_years: np.ndarray
     nrows = np.asarray([int(x.shape[0]) for x in sig], np.int64)
     offs = np.concatenate([[0], np.cumsum(nrows)[:-1]])
     if nat.is_device(beta) and all(x.is_cuda and x.stride(-1) == 1 for x in sig):
-        from ..ops.ridge import upload
-        if nat.hip_lib().pfml_aim_job_size() != AIM_JOB.itemsize:
-            raise RuntimeError("AimJob layout mismatch between python and libpfml_hip")
-        jobs = np.zeros(J, AIM_JOB)
-        jobs["s"] = [x.data_ptr() for x in sig]
-        jobs["ld"] = [x.stride(0) for x in sig]
-        jobs["off"] = offs
-        jobs["nrow"] = nrows
-        jobs["nk"] = [m[3] + 1 for m in meta]
-        (dj,) = upload([jobs], beta.device)
         w = torch.empty(int(nrows.sum()), dtype=torch.float64, device=beta.device)
-        nat.check(nat.hip_lib().pfml_aim_gemv(dj.data_ptr(), J, int(nrows.max()),
-                                              coefs.data_ptr(), coefs.shape[1], w.data_ptr(),
-                                              nat.stream_of(beta)), "pfml_aim_gemv")
-        w_all = w.cpu().numpy()
+        w_all = _aim_gemv(sig, coefs, [m[3] + 1 for m in meta], offs, w).cpu().numpy()
     else:
         w_all = torch.cat([s_[:, : m[3] + 1] @ coefs[k, : m[3] + 1].to(s_.device)
                            for k, (s_, m) in enumerate(zip(sig, meta))]).cpu().numpy()
@@ -632,19 +647,7 @@ def backtest_device(cfg: Config, grid, inputs, layout: dict, wealth: pd.DataFram
     Na = N if direct else max(int(nsig.max()) if B else 1, 1)
     wa = torch.zeros((B, Na), **f64)
     if B and dev.type == "cuda" and all(x.is_cuda and x.stride(-1) == 1 for x in sig):
-        from ..ops.ridge import upload
-        if nat.hip_lib().pfml_aim_job_size() != AIM_JOB.itemsize:
-            raise RuntimeError("AimJob layout mismatch between python and libpfml_hip")
-        jobs = np.zeros(B, AIM_JOB)
-        jobs["s"] = [x.data_ptr() for x in sig]
-        jobs["ld"] = [x.stride(0) for x in sig]
-        jobs["off"] = np.arange(B, dtype=np.int64) * Na
-        jobs["nrow"] = nsig
-        jobs["nk"] = [m[2] + 1 for m in meta]
-        (dj,) = upload([jobs], dev)
-        nat.check(nat.hip_lib().pfml_aim_gemv(dj.data_ptr(), B, int(nsig.max()),
-                                              coefs.data_ptr(), coefs.shape[1], wa.data_ptr(),
-                                              nat.stream_of(wa)), "pfml_aim_gemv")
+        _aim_gemv(sig, coefs, [m[2] + 1 for m in meta], np.arange(B, dtype=np.int64) * Na, wa)
     else:
         for t, (s_, m) in enumerate(zip(sig, meta)):
             wa[t, : s_.shape[0]] = (s_[:, : m[2] + 1] @ coefs[t, : m[2] + 1].to(s_.device)).to(dev)
