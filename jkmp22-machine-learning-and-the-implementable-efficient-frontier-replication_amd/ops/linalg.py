@@ -7,6 +7,9 @@
 * ``sqrtm_spd``    - principal square root by the scaled product-form Denman-Beavers
                      iteration (inverses + GEMMs only).  Replaces scipy.linalg.sqrtm (Schur,
                      General_functions.py:956): the argument sigma_hat^2 - 4I is symmetric PSD.
+* ``eigh_psd``     - symmetric PSD eigendecomposition by batched one-sided Jacobi
+                     (csrc/eigh_jacobi.hip); ``m_tilde0_eig``: m_tilde_0 = V f(E) V' from it,
+                     the root of the m_func repair (nothing squares cond(x)).
 * ``solve``        - general (non-symmetric) batched solve with partial pivoting, K7.
 * ``m_func``       - trading-speed matrix m of Lemma 1 (General_functions.py:919-963), batched
                      over months with block-diagonal padding for ragged universes.
@@ -667,6 +670,143 @@ def _db_check(M: torch.Tensor, tol: float, status: torch.Tensor | None) -> None:
                                           status.data_ptr(), nat.stream_of(M)), "pfml_db_check")
 
 
+# ---------------------------------------------------------------------------------------
+# Symmetric PSD eigendecomposition (csrc/eigh_jacobi.hip) and the eigen form of m_tilde_0
+# ---------------------------------------------------------------------------------------
+# the m_func repair's m_tilde_0 from the device eigendecomposition of x (0: the host's
+# convergence-checked Denman-Beavers root of x^2 + 4x, the former repair)
+MFUNC_REPAIR_EIG = os.environ.get("PFML_MFUNC_REPAIR_EIG", "1") != "0"
+EIGH_UNIT_ROUNDOFF = 2.0 ** -53
+nat.register_hip("pfml_eigh_psd_max_n", [])
+nat.register_hip("pfml_eigh_psd_block_cols", [C.c_int])
+nat.register_hip("pfml_eigh_psd_rounds", [C.c_int])
+nat.register_hip("pfml_eigh_psd_pairs", [C.c_int])
+nat.register_hip("pfml_eigh_psd_lds_bytes", [C.c_int], C.c_int64)
+nat.register_hip("pfml_eigh_psd_floor", [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p,
+                                         C.c_void_p])
+nat.register_hip("pfml_eigh_psd_round", [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
+                                         C.c_void_p])
+nat.register_hip("pfml_eigh_psd_finish", [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p])
+
+
+def eigh_psd_max_n() -> int:
+    """Largest N the device eigensolver serves (1152: the LDS bound of its narrowest blocks)."""
+    return int(nat.hip_lib().pfml_eigh_psd_max_n())
+
+
+def _eigh_psd_device(A: torch.Tensor, max_sweeps: int, status: torch.Tensor | None,
+                     want_f: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor | None, int]:
+    """The device sweeps of ``eigh_psd``: (e, Vt, f(e) or None, sweeps taken)."""
+    lib = nat.hip_lib()
+    B, N, _ = A.shape
+    if N > eigh_psd_max_n():
+        raise ValueError(f"eigh_psd: N = {N} is beyond the device solver's "
+                         f"{eigh_psd_max_n()} columns")
+    if A.dtype != torch.float64:
+        raise ValueError("eigh_psd: the device solver is fp64 only")
+    dev, st = A.device, nat.stream_of(A)
+    G = A.contiguous().clone()
+    Vt = torch.eye(N, dtype=A.dtype, device=dev).repeat(B, 1, 1)
+    e = torch.empty((B, N), dtype=A.dtype, device=dev)
+    f = torch.empty_like(e) if want_f else None
+    rounds, pairs = lib.pfml_eigh_psd_rounds(N), lib.pfml_eigh_psd_pairs(N)
+    meas = torch.zeros((B, pairs), dtype=A.dtype, device=dev)
+    tol = N * EIGH_UNIT_ROUNDOFF
+    floor2 = torch.empty(B, dtype=A.dtype, device=dev)       # (tol max_j |a_j|)^2 per matrix
+    nat.check(lib.pfml_eigh_psd_floor(G.data_ptr(), B, N, tol, floor2.data_ptr(), st),
+              "pfml_eigh_psd_floor")
+    # a matrix with a non-finite entry is refused before the first sweep; ``done`` (refused or
+    # converged) matrices are skipped by the kernel
+    refused = ~torch.isfinite(A).reshape(B, -1).all(dim=1)
+    done = refused.to(torch.int32)
+    sweeps = 0
+    while sweeps < max_sweeps and not bool(done.all()):     # the one host read per sweep
+        for r in range(rounds):
+            # (a sweep: N (N - 1) / 2 column pairs of three dot products and four row updates)
+            _work.add("eigh_round_kernel", 9.0 * B * N ** 3 / rounds, 8.0 * B * 4 * N * N)
+            nat.check(lib.pfml_eigh_psd_round(G.data_ptr(), Vt.data_ptr(), B, N, r,
+                                              done.data_ptr(), floor2.data_ptr(), tol,
+                                              meas.data_ptr(), st),
+                      "pfml_eigh_psd_round")
+        sweeps += 1
+        # (torch.maximum / max propagate NaN; NaN <= tol is False: not converged)
+        conv = (meas.max(dim=1).values <= tol).to(torch.int32)
+        done = torch.maximum(done, conv)
+    nat.check(lib.pfml_eigh_psd_finish(G.data_ptr(), Vt.data_ptr(), B, N, floor2.data_ptr(),
+                                       e.data_ptr(), nat.ptr(f), st), "pfml_eigh_psd_finish")
+    if status is not None:
+        status |= (refused | (done == 0)).to(status.dtype)
+    return e, Vt, f, sweeps
+
+
+def eigh_psd(A: torch.Tensor, *, max_sweeps: int = 30, status: torch.Tensor | None = None,
+             sort: bool = False, info: dict | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """Eigendecomposition of a batch A [B, N, N] of symmetric positive semi-definite matrices:
+    (e [B, N], Vt [B, N, N]) with A = Vt' diag(e) Vt - ROW j of Vt is the eigenvector of e_j.
+    A is not modified.  The eigenvalues come in no particular order unless ``sort`` (ascending,
+    a gather; off the hot path).
+
+    Device: batched one-sided (Hestenes) Jacobi (csrc/eigh_jacobi.hip) for 1 <= N <= 1152
+    (ValueError beyond): block rounds until no column pair of any matrix exceeds
+    |g_p . g_q| <= N u |g_p| |g_q| (columns under N u max_j |a_j| are left alone: zero
+    eigenvalues of a singular A), at most ``max_sweeps`` sweeps, one host read per sweep.
+    The arithmetic order is fixed: a matrix's result is bitwise the same whatever batch it is
+    in.  ``status`` (a [B] int32 tensor) gets 1 for a matrix with a non-finite entry (refused
+    before the first sweep; its e and Vt are meaningless) and for one still unconverged after
+    ``max_sweeps``.  e_j carries the sign of v_j' A v_j, so a rounding-level negative
+    eigenvalue of a PSD input comes back negative.  ``info`` (a dict): gets ``sweeps``, the
+    number of sweeps the call took.
+
+    Symmetric INDEFINITE input is out of scope: a one-sided method orthogonalises the columns
+    of A, i.e. diagonalises A^2, and a pair of eigenvalues +l, -l of equal magnitude does not
+    separate (their eigenvectors come back mixed).
+
+    CPU tensors: ``torch.linalg.eigh`` in the same layout (ascending; status untouched)."""
+    if A.dim() != 3 or A.shape[-1] != A.shape[-2] or A.shape[-1] < 1:
+        raise ValueError("eigh_psd: a [B, N, N] batch with N >= 1 is required")
+    if not nat.is_device(A):
+        e, V = torch.linalg.eigh(A)
+        return e, V.transpose(-1, -2).contiguous()
+    e, Vt, _, sweeps = _eigh_psd_device(A, max_sweeps, status, False)
+    if info is not None:
+        info["sweeps"] = sweeps
+    if sort:
+        e, idx = torch.sort(e, dim=-1)
+        Vt = torch.gather(Vt, 1, idx.unsqueeze(-1).expand_as(Vt))
+    return e, Vt
+
+
+def _m0_of_eig(e: torch.Tensor) -> torch.Tensor:
+    x = e.clamp_min(0.0)
+    return 2.0 / (x + 2.0 + torch.sqrt(x * x + 4.0 * x))
+
+
+def m_tilde0_eig(x: torch.Tensor, status: torch.Tensor | None = None) -> torch.Tensor:
+    """m_tilde_0 = 1/2 (sigma_hat - sqrtm(sigma_hat^2 - 4I)), sigma_hat = x + 2I
+    (General_functions.py:955-956), from the eigendecomposition x = V E V' of the symmetric PSD
+    x [B, N, N] itself: V f(E) V' with f(e) = 2 / (e + 2 + sqrt(e^2 + 4e)) - the same function,
+    free of cancellation, and nothing squares cond(x).  Eigenvalues are clamped at 0 before f.
+
+    On the device an eigenvalue under the solver's floor, N u max_j |x_j| <= N u |x|_2, counts
+    as 0 (f = 1): the solver does not resolve it, and f ~ 1 - sqrt(e) has an infinite slope
+    there.  The floor is relative to |x|_2 while f depends on the absolute e, so the result
+    equals V f(E) V' only for cond(x) < 1 / (N u) (2e13 at N = 496), or where the eigenvalues
+    under the floor are exact zeros; beyond that an eigenvalue that is small against |x|_2
+    but not against 1 is taken as 0 (e = 1e-3 under |x|_2 = 1e12: f = 1 for 0.97).  x of
+    m_func has cond 1e10 at wealth 1, and the ten fixed-point steps forget the start.
+    One ``eigh_psd`` and one symmetric-mode product (exactly symmetric result); ``status`` as
+    in ``eigh_psd``."""
+    out = torch.empty_like(x)
+    if nat.is_device(x):
+        _, Vt, f, _ = _eigh_psd_device(x, 30, status, True)
+    else:
+        e, Vt = eigh_psd(x)
+        f = _m0_of_eig(e)
+    return gemm_fused(Vt, Vt, out, trans_a=True, k_scale=f, sym=True)
+
+
 def m_tilde(sigma: torch.Tensor, lam: torch.Tensor, w: torch.Tensor, rf: torch.Tensor,
             mu: float, gamma: float, iterations: int = 10, mask: torch.Tensor | None = None,
             db_iters: int = DB_ITERS, status: torch.Tensor | None = None,
@@ -757,22 +897,47 @@ def m_func_reference(sigma: torch.Tensor, lam: torch.Tensor, w: torch.Tensor, rf
 
     m_tilde_0 = 1/2 (sigma_hat - sqrtm(sigma_hat^2 - 4I)) is evaluated in the algebraically
     identical, cancellation-free form 2 (sigma_hat + sqrtm(sigma_hat^2 - 4I))^-1.
+
+    Device tensors: m_tilde_0 comes from ``m_tilde0_eig`` (the same function of x through its
+    eigendecomposition; counted as linalg.m_func_repair_eig), and only a matrix the eigensolver
+    flags takes the host square root (linalg.eigh_not_converged).  The eigensolver serves
+    N <= 1152 (``eigh_psd_max_n``); wider matrices take the host square root as well
+    (linalg.m_func_repair_host_wide).  PFML_MFUNC_REPAIR_EIG=0: the host square root for all.  The CPU branch is the oracle and does not change.
     """
     B, N, _ = sigma.shape
     dt = sigma.dtype
     if mask is None:
         mask = torch.ones((B, N), dtype=dt, device=sigma.device)
     c = (1.0 + rf + mu).view(B, 1, 1)
-    I = _eye_like(sigma)
     sig = _sym(sigma)
     sig_gr = mask.unsqueeze(-1) * mask.unsqueeze(-2) + sig / (c * c)
     a = lam.rsqrt()                                              # Lambda^-1/2 diagonal
     x = (gamma / w).view(B, 1, 1) * sig * a.unsqueeze(-1) * a.unsqueeze(-2)
     ydiag = 1.0 + torch.diagonal(sig_gr, dim1=-2, dim2=-1)
-    sig_hat = x + 2.0 * I
-    S = _sym(x @ x + 4.0 * x)
-    root = sqrtm_spd(S.cpu()).to(sigma.device) if nat.is_device(S) else sqrtm_spd(S)
-    mt = 2.0 * torch.linalg.inv(_sym(sig_hat + root))
+
+    def m0_root(xs):
+        S = _sym(xs @ xs + 4.0 * xs)
+        root = sqrtm_spd(S.cpu()).to(sigma.device) if nat.is_device(S) else sqrtm_spd(S)
+        return 2.0 * torch.linalg.inv(_sym(xs + 2.0 * _eye_like(xs) + root))
+
+    if nat.is_device(sigma) and MFUNC_REPAIR_EIG and N > eigh_psd_max_n():
+        # (wider than the device eigensolver serves: the host root, as before it existed)
+        COUNTERS.add("linalg.m_func_repair_host_wide", B)
+        mt = m0_root(x)
+    elif nat.is_device(sigma) and MFUNC_REPAIR_EIG:
+        # m_tilde_0 from the device eigendecomposition of x itself: x^2 + 4x squares cond(x),
+        # 1e10 at wealth 1, and the host root of it (m0_root) is what a repair spent its time
+        # in; only a matrix the eigensolver flags still takes it
+        est = torch.zeros(B, dtype=torch.int32, device=sigma.device)
+        mt = m_tilde0_eig(_sym(x), est)
+        bad = torch.nonzero(est).flatten()
+        if bad.numel():
+            COUNTERS.add("linalg.eigh_not_converged", int(bad.numel()))
+            mt[bad] = m0_root(x[bad])
+        if B - bad.numel():
+            COUNTERS.add("linalg.m_func_repair_eig", int(B - bad.numel()))
+    else:
+        mt = m0_root(x)
     base = x + torch.diag_embed(ydiag)
     for _ in range(iterations):
         mt = torch.linalg.inv(_sym(base - _sym(mt) * sig_gr))

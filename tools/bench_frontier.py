@@ -19,6 +19,12 @@ relative difference of the two arms' pf_summary rows, the peak device memory all
 the point (the frontier arm alone: the counter is reset after the stage arm).
 
     python tools/bench_frontier.py --out profiles/r09_frontier.json
+
+The wealth = 1 column alone, with the m_func repair's share of each point (the seconds inside
+``linalg.m_func_reference``, device synchronised around each call) and the eigensolver's sweeps
+per repair chunk - PFML_MFUNC_REPAIR_EIG=0 in the environment is the host-root arm:
+
+    python tools/bench_frontier.py --set ef.wealth=[1.0] --loop-points 0 --repair-detail
 """
 import argparse
 import gc
@@ -49,6 +55,8 @@ def main():
                     help="points that also go through the stage loop (-1: all)")
     ap.add_argument("--set", action="append", default=[], help="dotted override key=value")
     ap.add_argument("--out", default="", help="write the JSON here as well")
+    ap.add_argument("--repair-detail", action="store_true",
+                    help="time the m_func repair calls and record the eigensolver's sweeps")
     a = ap.parse_args()
     from pfml.config import Config
     from pfml.data import io
@@ -108,6 +116,27 @@ def main():
     # ---- the two arms, alternating point by point --------------------------------------
     tmp = tempfile.mkdtemp(prefix="pfml_ef_bench_")
     points = []
+    repair = {"s": 0.0, "calls": 0, "matrices": 0, "sweeps": []}
+    if a.repair_detail:
+        from pfml.ops import linalg as la
+        inner, inner_eigh = la.m_func_reference, la._eigh_psd_device
+
+        def timed_repair(sigma, *args, **kw):
+            sync()
+            t = time.perf_counter()
+            r = inner(sigma, *args, **kw)
+            sync()
+            repair["s"] += time.perf_counter() - t
+            repair["calls"] += 1
+            repair["matrices"] += int(sigma.shape[0])
+            return r
+
+        def counted_eigh(*args, **kw):
+            r = inner_eigh(*args, **kw)
+            repair["sweeps"].append(int(r[3]))
+            return r
+
+        la.m_func_reference, la._eigh_psd_device = timed_repair, counted_eigh
 
     def stage_arm(W, gam):
         cfg_pt = frontier.point_config(cfg, W, gam)
@@ -132,6 +161,12 @@ def main():
                "s4_fallbacks": json.loads(row["s4_fallbacks"]),
                "grid_recomputed_cells": row["grid_recomputed_cells"],
                "finite": bool(np.isfinite([row[c] for c in NUM]).all())}
+        if a.repair_detail:
+            rec.update(repair_s=round(repair["s"], 4),
+                       repair_share=round(repair["s"] / max(row["seconds"], 1e-300), 3),
+                       repair_calls=repair["calls"],
+                       repair_matrices=repair["matrices"], eigh_sweeps=repair["sweeps"])
+            repair.update(s=0.0, calls=0, matrices=0, sweeps=[])
         if cuda:
             rec["peak_device_bytes"] = int(torch.cuda.max_memory_allocated(dev))
             rec["allocated_after_bytes"] = int(torch.cuda.memory_allocated(dev))
