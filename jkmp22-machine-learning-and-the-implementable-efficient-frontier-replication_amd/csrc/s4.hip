@@ -12,7 +12,6 @@
 //             with sigma_gr = mask mask' + sym(Sigma)/c^2 and y_i = 1 + sigma_gr_ii, all formed
 //             from Sigma on the fly (no sigma_gr / x / base matrices are stored)
 //   MF_DB     M'   = I/2 + (mu^2 sym(M) + mu^-2 sym(Minv))/4    (Denman-Beavers update)
-//   MF_SHAT   out  = sym(X) + d I                                (sigma_hat = x + 2I, root + sigma_hat)
 //   MF_M0     out  = (sym(X) + d I - sym(Y)) / 2                 (m_tilde_0 = (sigma_hat - root) / 2,
 //             the reference's own form, General_functions.py:955)
 //
@@ -26,23 +25,45 @@ typedef double double2_t __attribute__((ext_vector_type(2)));
 
 constexpr int TS = 32;
 
-enum Mode { MF_X = 0, MF_FIX = 1, MF_DB = 2, MF_SHAT = 3, MF_M0 = 4 };
+enum Mode { MF_X = 0, MF_FIX = 1, MF_DB = 2, MF_M0 = 4 };   // (3: a retired mode, refused)
 
 struct MfArgs {
   int mode, B, N;
   int64_t ld, sX;                 // layout of every [B, N, N] operand
-  const double* X;                // Sigma (X, FIX), M (DB), X (SHAT)
-  const double* Y;                // mt (FIX), Minv (DB), second addend (SHAT, may be null)
+  const double* X;                // Sigma (X, FIX), M (DB), x (M0)
+  const double* Y;                // mt (FIX), Minv (DB), root (M0); null for X
   double* out;
   const double* svec;             // [B] s (X, FIX) or mu (DB)
   const double* cvec;             // [B] c (FIX)
   const double* a;                // [B, N] lambda^-1/2 (X, FIX)
   const double* mask;             // [B, N] (FIX)
   int64_t sv;                     // batch stride of a / mask
-  double d;                       // diagonal add (SHAT)
+  double d;                       // diagonal add (M0)
   int flat;                       // X and Y exactly symmetric: sym() is the identity, so the
                                   // mirror tile is not read (half the loads)
 };
+
+// One element of a pass (header), shared by the tiled and the flat kernel.
+__device__ __forceinline__ double mf_value(const MfArgs& p, int i, int j, double xs, double ys,
+                                           double s, double c, double ai, double aj, double mi,
+                                           double mj) {
+  double v;
+  if (p.mode == MF_X) {
+    v = s * (ai * aj) * xs;
+  } else if (p.mode == MF_FIX) {
+    const double ic2 = 1.0 / (c * c);
+    const double mm = mi * mj;
+    v = xs * (s * (ai * aj) - ys * ic2) - ys * mm;
+    if (i == j) v += 1.0 + mm + xs * ic2;
+  } else if (p.mode == MF_DB) {
+    const double mu2 = s * s;
+    v = 0.25 * (mu2 * xs + ys / mu2);
+    if (i == j) v += 0.5;
+  } else {                                         // MF_M0 (the host refuses any other mode)
+    v = 0.5 * ((i == j ? xs + p.d : xs) - ys);
+  }
+  return v;
+}
 
 // (A form with one workgroup per tile PAIR - every element read once per operand, the mirror
 // written through an LDS transpose - measured slower: 27.6 vs 25.7 ms per S4 run, the
@@ -76,59 +97,18 @@ __global__ __launch_bounds__(256) void mfunc_sym_kernel(MfArgs p) {
     const int64_t o = (int64_t)i * p.ld + j;
     const double xs = p.flat ? X[o] : 0.5 * (X[o] + tx[r][tx_]);
     const double ys = Y ? (p.flat ? Y[o] : 0.5 * (Y[o] + ty[r][tx_])) : 0.0;
-    double v;
-    if (p.mode == MF_X) {
-      v = s * (av[i] * av[j]) * xs;
-    } else if (p.mode == MF_FIX) {
-      const double ic2 = 1.0 / (c * c);
-      const double mm = mv[i] * mv[j];
-      v = xs * (s * (av[i] * av[j]) - ys * ic2) - ys * mm;
-      if (i == j) v += 1.0 + mm + xs * ic2;
-    } else if (p.mode == MF_DB) {
-      const double mu2 = s * s;
-      v = 0.25 * (mu2 * xs + ys / mu2);
-      if (i == j) v += 0.5;
-    } else if (p.mode == MF_M0) {
-      v = 0.5 * ((i == j ? xs + p.d : xs) - ys);
-    } else {
-      v = xs + ys;
-      if (i == j) v += p.d;
-    }
-    O[o] = v;
+    O[o] = mf_value(p, i, j, xs, ys, s, c, av ? av[i] : 0.0, av ? av[j] : 0.0,
+                    mv ? mv[i] : 0.0, mv ? mv[j] : 0.0);
   }
 }
 
 // The flat passes (X and Y exactly symmetric: no mirror tile) as a row stream: one wave per
 // row, 16-byte loads / stores of column pairs (all of a row's loads issued before its first
-// store), the row's a_i / mask_i wave-uniform, the column vectors loaded once per wave.  Same
-// expressions as mfunc_sym_kernel (bitwise), ~1.4x its rate: the 32 x 32 tile form spends a
+// store), the row's a_i / mask_i wave-uniform, the column vectors loaded once per wave.  The same
+// mf_value as mfunc_sym_kernel (bitwise), ~1.4x its rate: the 32 x 32 tile form spends a
 // 256-thread workgroup on 1024 elements with 8-byte accesses.  Needs even N <= 512, even ld and
 // 16-byte aligned operands (host checks; otherwise the tiled form runs).
 constexpr int FLAT_ROWS = 16;                      // rows per workgroup (4 per wave)
-
-__device__ __forceinline__ double mf_value(const MfArgs& p, int i, int j, double xs, double ys,
-                                           double s, double c, double ai, double aj, double mi,
-                                           double mj) {
-  double v;
-  if (p.mode == MF_X) {
-    v = s * (ai * aj) * xs;
-  } else if (p.mode == MF_FIX) {
-    const double ic2 = 1.0 / (c * c);
-    const double mm = mi * mj;
-    v = xs * (s * (ai * aj) - ys * ic2) - ys * mm;
-    if (i == j) v += 1.0 + mm + xs * ic2;
-  } else if (p.mode == MF_DB) {
-    const double mu2 = s * s;
-    v = 0.25 * (mu2 * xs + ys / mu2);
-    if (i == j) v += 0.5;
-  } else if (p.mode == MF_M0) {
-    v = 0.5 * ((i == j ? xs + p.d : xs) - ys);
-  } else {
-    v = xs + ys;
-    if (i == j) v += p.d;
-  }
-  return v;
-}
 
 // (even N: every lane handles whole column pairs; N <= 64 * 2 * QM per wave pass)
 constexpr int FLAT_QM = 4;                         // column-pair chunks per lane (N <= 512)
@@ -306,6 +286,8 @@ struct PfmlMfArgs {
 extern "C" int pfml_mf_args_size() { return (int)sizeof(PfmlMfArgs); }
 
 extern "C" hipError_t pfml_mfunc_sym(const PfmlMfArgs* h, hipStream_t st) {
+  if (h->mode != MF_X && h->mode != MF_FIX && h->mode != MF_DB && h->mode != MF_M0)
+    return hipErrorInvalidValue;
   if (h->B <= 0 || h->N <= 0) return hipSuccess;
   if (h->out == h->X || (h->Y && h->out == h->Y)) return hipErrorInvalidValue;   // tiles race
   MfArgs p{h->mode, h->B, h->N, h->ld, h->sX, h->X, h->Y, h->out, h->svec, h->cvec, h->a,

@@ -220,7 +220,7 @@ extern "C" hipError_t pfml_spd_inverse(double* A, int n, int64_t lda, int64_t sA
 
 // ---------------------------------------------------------------------------------------
 // Leaves of the recursive Schur-complement inverse (the production form for n >= 160, host
-// orchestration in ops/linalg.py::_spd_inverse_recursive: every off-diagonal product one
+// orchestration in ops/linalg.py::_schur_inverse: every off-diagonal product one
 // fused GEMM, csrc/gemm_f64.hip).  (Blocked Gauss-Jordan forms with 64- / 128-wide pivot
 // blocks and a fused sign-symmetric form measured 2.1 / 3.0 / 2.4x slower on [256, 490, 490],
 // profiles/r02_inverse_variants_v2.json, and were removed.)

@@ -3,7 +3,8 @@
 * ``spd_inverse``  - SPD inverse (csrc/spd_inverse.hip): recursive Schur-complement form over
                      64 x 64 register Gauss-Jordan leaves for n >= 160, blocked Gauss-Jordan
                      below; matrices whose pivots are not positive fall back to a pivoted LU
-                     inverse (counted).
+                     inverse (counted).  ``spd_inverse_sym``: the one-triangle form of the same
+                     recursion (``_schur_inverse``), the one the device m_func runs.
 * ``sqrtm_spd``    - principal square root by the scaled product-form Denman-Beavers
                      iteration (inverses + GEMMs only).  Replaces scipy.linalg.sqrtm (Schur,
                      General_functions.py:956): the argument sigma_hat^2 - 4I is symmetric PSD.
@@ -31,18 +32,6 @@ def _eye_like(A: torch.Tensor) -> torch.Tensor:
     return torch.eye(A.shape[-1], dtype=A.dtype, device=A.device).expand_as(A)
 
 
-def spd_inverse_into(A: torch.Tensor, out: torch.Tensor, status: torch.Tensor) -> torch.Tensor:
-    """out = A^-1 for a device batch [B, n, n] of SPD matrices without modifying or copying A
-    (the recursive form reads A and writes only ``out``); other forms copy A into out first.
-    Non-positive pivots are flagged in ``status`` (no host sync)."""
-    B, n, _ = A.shape
-    if nat.is_device(A) and n >= _BLOCKED_MIN_N and A.is_contiguous() and out.is_contiguous():
-        _spd_inverse_recursive(out, status, src=A)
-        return out
-    out.copy_(A)
-    return spd_inverse(out, inplace=True, status=status)
-
-
 def spd_inverse(A: torch.Tensor, inplace: bool = False,
                 status: torch.Tensor | None = None) -> torch.Tensor:
     """Inverse of a batch [B, n, n] of SPD matrices.
@@ -63,7 +52,7 @@ def spd_inverse(A: torch.Tensor, inplace: bool = False,
         lib = nat.hip_lib()
         st = status if status is not None else torch.zeros(B, dtype=torch.int32, device=X.device)
         if n >= _BLOCKED_MIN_N:
-            _spd_inverse_recursive(X, st)
+            _schur_inverse(X, st)
         else:
             work = torch.empty(lib.pfml_spd_inverse_work_doubles(n, B), dtype=torch.float64,
                                device=X.device)
@@ -109,8 +98,8 @@ def _rec_split(n: int) -> int:
     return _REC_LEAF * ((n + 2 * _REC_LEAF - 1) // (2 * _REC_LEAF))
 
 
-def _spd_inverse_recursive(X: torch.Tensor, status: torch.Tensor,
-                           src: torch.Tensor | None = None) -> None:
+def _schur_inverse(X: torch.Tensor, status: torch.Tensor, src: torch.Tensor | None = None,
+                   sym: bool = False, node: bool = True) -> None:
     """SPD inverse by recursive 2 x 2 Schur-complement blocks, into X (from ``src`` when given:
     the source is only read, so no copy of it is made; else in place):
 
@@ -123,92 +112,20 @@ def _spd_inverse_recursive(X: torch.Tensor, status: torch.Tensor,
     per 64 columns; the 64 x 64 leaves are the register-resident leaf kernel
     (csrc/spd_inverse.hip).  Schur complements of an SPD matrix are SPD, so no pivoting; a
     non-positive leaf pivot flags ``status`` like the other forms.  One W buffer per depth
-    (the parent's W lives across the child's recursion)."""
+    (the parent's W lives across the child's recursion).
+
+    ``sym`` (``spd_inverse_sym``): S and the X11 update on their lower tiles only and mirrored,
+    X21 = X12' written by the X12 launch, symmetric leaves - about n^3 flops instead of
+    ~1.67 n^3, and an exactly symmetric result.  ``node``: its nodes of 65..128 rows in one
+    launch (spd_node_sym_kernel: both leaves and the four products in LDS, bitwise the GEMM +
+    leaf launches it replaces, which ``node=False`` takes)."""
     lib = nat.hip_lib()
     B, n, _ = X.shape
     st = nat.stream_of(X)
     ld, sX = X.stride(1), X.stride(0)
 
     def buf(depth, h, m):
-        key = (X.device, B, depth, _buf_tag(X))
-        w = _REC_BUFS.get(key)
-        if w is None or w.numel() < B * h * m:
-            w = torch.empty(B * h * m, dtype=torch.float64, device=X.device)
-            _REC_BUFS[key] = w
-        return w[:B * h * m].view(B, h, m)
-
-    def rec(r0, nn, depth, A):
-        if nn <= _REC_LEAF:
-            _work.add("spd_leafinv_kernel", 2.0 * B * nn ** 3, 16.0 * B * nn * nn)
-            nat.check(lib.pfml_spd_leafinv_to(A.data_ptr(), A.stride(1), A.stride(0),
-                                              X.data_ptr(), ld, sX, B, r0, nn,
-                                              status.data_ptr(), 0, st), "pfml_spd_leafinv_to")
-            return
-        h = _rec_split(nn)
-        m = nn - h
-        a, c, e = r0, r0 + h, r0 + nn
-        rec(a, h, depth + 1, A)
-        W = buf(depth, h, m)
-        gemm_fused(X[:, a:c, a:c], A[:, a:c, c:e], W)                        # W = X11 A12
-        if A is X:
-            gemm_fused(X[:, c:e, a:c], W, X[:, c:e, c:e], alpha=-1.0, beta=1.0)  # S
-        else:
-            gemm_fused(A[:, c:e, a:c], W, X[:, c:e, c:e], alpha=-1.0,
-                       addend=A[:, c:e, c:e], addend_cols=m)                  # S = A22 - A21 W
-        rec(c, m, depth + 1, X)
-        gemm_fused(W, X[:, c:e, c:e], X[:, a:c, c:e], alpha=-1.0)            # X12
-        # X21 = -X22 W' as its own product, not X12^T: the two carry independent rounding,
-        # and the Denman-Beavers iterate Y M^-1 (which sees both triangles) measured 20x
-        # closer to eigh with the product (2e-10 -> < 1e-11 on tests/test_gpu_pipeline.py)
-        gemm_fused(X[:, c:e, c:e], W, X[:, c:e, a:c], trans_b=True, alpha=-1.0)
-        gemm_fused(X[:, a:c, c:e], W, X[:, a:c, a:c], trans_b=True, alpha=-1.0,
-                   beta=1.0)                                                  # X11 -= X12 W'
-
-    rec(0, n, 0, X if src is None else src)
-
-
-# GEMM tile config of the symmetric form's products (csrc/gemm_f64.hip tile_cfg; 0: auto);
-# PFML_SPD_SYM=0 takes the two-sided form for every m_func inverse, PFML_DB_SYM=0 /
-# PFML_DB_SYMPROD=0 the two-sided inverse / product inside Denman-Beavers (A/B switches)
-SYM_GEMM_CFG = int(os.environ.get("PFML_SYM_GEMM_CFG", "0"))
-SYM_INVERSE = os.environ.get("PFML_SPD_SYM", "1") != "0"
-DB_SYM = os.environ.get("PFML_DB_SYM", "1") != "0"
-DB_SYMPROD = os.environ.get("PFML_DB_SYMPROD", "1") != "0"
-# nodes of 65..128 rows in one launch (csrc/spd_inverse.hip spd_node_sym_kernel: both leaves and
-# the four products in LDS, bitwise the GEMM + leaf launches it replaces); 0: those launches
-SYM_NODE = os.environ.get("PFML_SPD_NODE", "1") != "0"
-
-
-def spd_inverse_sym(X: torch.Tensor, status: torch.Tensor,
-                    src: torch.Tensor | None = None) -> torch.Tensor:
-    """In-place inverse of a device batch [B, n, n] of EXACTLY symmetric SPD matrices whose
-    result is used as a symmetric matrix (m_tilde_0 and the fixed-point steps of m_func,
-    General_functions.py:957-960): the recursive Schur form with every symmetric product
-    computed on its lower block triangle only and mirrored -
-
-        X11 = A11^-1,  W = X11 A12,  S = A22 - A21 W  (lower tiles),  X22 = S^-1,
-        X12 = -W X22  (X21 = X12' written by the same launch),  X11 -= X12 W'  (lower tiles)
-
-    about n^3 flops instead of the two-sided form's ~1.67 n^3, with exactly symmetric leaves
-    and products, so the result is exactly symmetric.  Non-positive pivots flag ``status``.
-    ``src`` (same shape, contiguous): the input, only read - the inverse goes to X without a
-    copy of the input first (the input blocks along the recursion's left spine and the A12 /
-    A21 / A22 blocks of its nodes are read from src; A22 enters the Schur GEMM as its addend,
-    the same arithmetic as the in-place beta)."""
-    B, n, _ = X.shape
-    if src is not None and (src.shape != X.shape or not src.is_contiguous()):
-        raise ValueError("spd_inverse_sym: src must be contiguous and shaped like X")
-    if not nat.is_device(X) or n < _BLOCKED_MIN_N or not X.is_contiguous() or not SYM_INVERSE:
-        if src is not None:
-            X.copy_(src)
-        return spd_inverse(X, inplace=True, status=status)
-    lib = nat.hip_lib()
-    st = nat.stream_of(X)
-    ld, sX = X.stride(1), X.stride(0)
-    cfg = SYM_GEMM_CFG
-
-    def buf(depth, h, m):
-        key = (X.device, B, depth, "sym", _buf_tag(X))
+        key = (X.device, B, depth, *(("sym",) if sym else ()), _buf_tag(X))
         w = _REC_BUFS.get(key)
         if w is None or w.numel() < B * h * m:
             w = torch.empty(B * h * m, dtype=torch.float64, device=X.device)
@@ -219,11 +136,12 @@ def spd_inverse_sym(X: torch.Tensor, status: torch.Tensor,
         # A: where this block's input lives (src along the left spine, else X itself)
         if nn <= _REC_LEAF:
             _work.add("spd_leafinv_kernel", 2.0 * B * nn ** 3, 16.0 * B * nn * nn)
-            nat.check(lib.pfml_spd_leafinv_to(A.data_ptr(), ld, sX, X.data_ptr(), ld, sX, B, r0,
-                                              nn, status.data_ptr(), 1, st),
+            nat.check(lib.pfml_spd_leafinv_to(A.data_ptr(), A.stride(1), A.stride(0),
+                                              X.data_ptr(), ld, sX, B, r0, nn,
+                                              status.data_ptr(), int(sym), st),
                       "pfml_spd_leafinv_to")
             return
-        if SYM_NODE and nn <= 2 * _REC_LEAF:
+        if sym and node and nn <= 2 * _REC_LEAF:
             m = nn - _REC_LEAF
             _work.add("spd_node_sym_kernel", B * (2.0 * _REC_LEAF ** 3 + 2.0 * m ** 3
                                                   + 3.0 * _REC_LEAF ** 2 * m
@@ -237,20 +155,60 @@ def spd_inverse_sym(X: torch.Tensor, status: torch.Tensor,
         a, c, e = r0, r0 + h, r0 + nn
         rec(a, h, depth + 1, A)
         W = buf(depth, h, m)
-        gemm_fused(X[:, a:c, a:c], A[:, a:c, c:e], W, tile_cfg=cfg)              # W = X11 A12
+        gemm_fused(X[:, a:c, a:c], A[:, a:c, c:e], W)                        # W = X11 A12
         if A is X:
-            gemm_fused(X[:, c:e, a:c], W, X[:, c:e, c:e], alpha=-1.0, beta=1.0, sym=True,
-                       tile_cfg=cfg)                                              # S
-        else:
+            gemm_fused(X[:, c:e, a:c], W, X[:, c:e, c:e], alpha=-1.0, beta=1.0, sym=sym)  # S
+        else:                          # (A22 as the addend: the same arithmetic as the beta)
             gemm_fused(A[:, c:e, a:c], W, X[:, c:e, c:e], alpha=-1.0, addend=A[:, c:e, c:e],
-                       sym=True, tile_cfg=cfg)                                    # S
+                       sym=sym)                                               # S = A22 - A21 W
         rec(c, m, depth + 1, X)
-        gemm_fused(W, X[:, c:e, c:e], X[:, a:c, c:e], alpha=-1.0, mirror_out=X[:, c:e, a:c],
-                   tile_cfg=cfg)                                                  # X12, X21
+        if sym:
+            gemm_fused(W, X[:, c:e, c:e], X[:, a:c, c:e], alpha=-1.0,
+                       mirror_out=X[:, c:e, a:c])                             # X12, X21
+        else:
+            gemm_fused(W, X[:, c:e, c:e], X[:, a:c, c:e], alpha=-1.0)        # X12
+            # X21 = -X22 W' as its own product, not X12^T: the two carry independent rounding,
+            # and the Denman-Beavers iterate Y M^-1 (which sees both triangles) measured 20x
+            # closer to eigh with the product (2e-10 -> < 1e-11 on tests/test_gpu_pipeline.py)
+            gemm_fused(X[:, c:e, c:e], W, X[:, c:e, a:c], trans_b=True, alpha=-1.0)
         gemm_fused(X[:, a:c, c:e], W, X[:, a:c, a:c], trans_b=True, alpha=-1.0, beta=1.0,
-                   sym=True, tile_cfg=cfg)                                        # X11 -= X12 W'
+                   sym=sym)                                                   # X11 -= X12 W'
 
     rec(0, n, 0, X if src is None else src)
+
+
+def _refuse_retired() -> None:
+    """The m_func A/B switches whose other arm was removed (profiles/r05_mfunc_db_accuracy.json,
+    r06_m0_form.json): a value that selected a removed arm is an error, not the other arm."""
+    gone = [k for k in ("PFML_SPD_SYM", "PFML_DB_SYM", "PFML_DB_SYMPROD", "PFML_M0_CANCEL",
+                        "PFML_SPD_NODE", "PFML_DB_NS_TAIL") if os.environ.get(k) == "0"]
+    if int(os.environ.get("PFML_SYM_GEMM_CFG") or 0) != 0:
+        gone.append("PFML_SYM_GEMM_CFG")
+    if gone:
+        raise ValueError(", ".join(f"{k}={os.environ[k]}" for k in gone) + ": retired - the "
+                         "m_func forms these values selected were removed")
+
+
+_refuse_retired()
+
+
+def spd_inverse_sym(X: torch.Tensor, status: torch.Tensor, src: torch.Tensor | None = None,
+                    node: bool = True) -> torch.Tensor:
+    """In-place inverse of a device batch [B, n, n] of EXACTLY symmetric SPD matrices whose
+    result is used as a symmetric matrix (m_tilde_0 and the fixed-point steps of m_func,
+    General_functions.py:957-960): the one-triangle form of ``_schur_inverse``, exactly
+    symmetric.  Non-positive pivots flag ``status``.  ``src`` (same shape, contiguous): the
+    input, only read - the inverse goes to X without a copy of the input first (the blocks
+    along the recursion's left spine and the A12 / A21 / A22 blocks of its nodes are read from
+    src).  ``node=False``: GEMM + leaf launches instead of one-launch nodes (same bits; tests)."""
+    B, n, _ = X.shape
+    if src is not None and (src.shape != X.shape or not src.is_contiguous()):
+        raise ValueError("spd_inverse_sym: src must be contiguous and shaped like X")
+    if not nat.is_device(X) or n < _BLOCKED_MIN_N or not X.is_contiguous():
+        if src is not None:
+            X.copy_(src)
+        return spd_inverse(X, inplace=True, status=status)
+    _schur_inverse(X, status, src=src, sym=True, node=node)
     return X
 
 
@@ -408,7 +366,7 @@ def sqrtm_spd(S: torch.Tensor, max_iter: int = 40, tol: float = 1e-13) -> torch.
 # ---------------------------------------------------------------------------------------
 # Fused symmetric passes (csrc/s4.hip) and the device m_func
 # ---------------------------------------------------------------------------------------
-MF_X, MF_FIX, MF_DB, MF_SHAT, MF_M0 = 0, 1, 2, 3, 4
+MF_X, MF_FIX, MF_DB, MF_M0 = 0, 1, 2, 4
 
 
 class _MfArgs(C.Structure):
@@ -476,7 +434,7 @@ def mf_sym(mode: int, X: torch.Tensor, Y: torch.Tensor | None, out: torch.Tensor
     elif mode == MF_M0:
         r = 0.5 * ((xs + d * eye) - ys)
     else:
-        r = xs + (ys if ys is not None else 0.0) + d * eye
+        raise ValueError(f"mf_sym: unknown mode {mode}")
     out.copy_(r)
     return out
 
@@ -580,13 +538,13 @@ def _db_mu(M: torch.Tensor, Minv: torch.Tensor, unscaled: bool, out: torch.Tenso
 
 
 def _db_sqrt(S: torch.Tensor, iters: int, scaled_iters: int, status: torch.Tensor | None,
-             ws: list, exact_sym: bool = False, ns_tail: bool | None = None) -> torch.Tensor:
+             ws: list, exact_sym: bool = False, ns_tail: bool = True) -> torch.Tensor:
     """sqrtm(S) by ``iters`` scaled product-form Denman-Beavers steps with NO host sync:
     norm scaling mu (computed on the device) for the first ``scaled_iters`` steps, then
     quadratically convergent unscaled steps.  ws: 4 [B, N, N] work buffers; ``exact_sym``: S is
     exactly symmetric (bit for bit).
 
-    ``ns_tail`` (default ``DB_NS_TAIL``): the last (unscaled) step takes M^-1 as its
+    ``ns_tail``: the last (unscaled) step takes M^-1 as its
     first-order Neumann form 2I - M - a Newton-Schulz step Y <- (3Y - Y M) / 2, one product
     and NO inverse, whose error against the exact step is O(|M - I|^2).  By then M is the
     identity to 1e-16 .. 1e-10 on production spectra (cond(x^2 + 4x) up to 7e14,
@@ -598,8 +556,6 @@ def _db_sqrt(S: torch.Tensor, iters: int, scaled_iters: int, status: torch.Tenso
     mu = torch.empty(B, dtype=S.dtype, device=S.device)
     rs = torch.empty((B, N), dtype=S.dtype, device=S.device)     # Y update row scales
     es = torch.empty((B, N), dtype=S.dtype, device=S.device)
-    if ns_tail is None:
-        ns_tail = DB_NS_TAIL
     ns_tail = ns_tail and iters > scaled_iters
     # the first (exact) step reads S itself as both M and Y - no copies; its M update goes to
     # the unused buffer ``spare`` (S is only read)
@@ -610,36 +566,36 @@ def _db_sqrt(S: torch.Tensor, iters: int, scaled_iters: int, status: torch.Tenso
         M.copy_(S)
         Y.copy_(S)
     # S, M, M^-1 and Y are symmetric (M, Y are polynomials in S; in exact arithmetic Y and M^-1
-    # commute, so Y M^-1 is symmetric too).  sym_inv: M^-1 by the one-triangle inverse;
-    # sym_prod: Y M^-1 on its lower tiles, mirrored.  With both (and S exactly symmetric, as
-    # m_tilde builds it; after the first M update otherwise) every iterate is EXACTLY symmetric
-    # and the M update skips its mirror reads (flat).  profiles/r05_mfunc_db_accuracy.json: m
-    # vs the reference form 4e-14 (two-sided products: 3e-14); S4 -12 ms.
+    # commute, so Y M^-1 is symmetric too).  dev_sym: M^-1 by the one-triangle inverse and
+    # Y M^-1 on its lower tiles, mirrored.  With S exactly symmetric (as m_tilde builds it;
+    # after the first M update otherwise) every iterate is then EXACTLY symmetric and the M
+    # update skips its mirror reads (flat).  profiles/r05_mfunc_db_accuracy.json: m vs the
+    # reference form 4e-14 (two-sided products: 3e-14); S4 -12 ms.
     dev_sym = nat.is_device(M) and N >= _BLOCKED_MIN_N
-    sym_inv, sym_prod = DB_SYM and dev_sym, DB_SYMPROD and dev_sym
     for it in range(iters):
         if ns_tail and it == iters - 1:
             # Newton-Schulz tail: Y' = 1.5 Y - 0.5 Y M (Y M symmetric, as Y M^-1 is)
             _db_check(M, DB_TAIL_TOL, status)
             rs.fill_(-0.5)
             es.fill_(1.5)
-            gemm_fused(Y, M, Yn, row_scale=rs, addend=Y, addend_row_scale=es, sym=sym_prod)
+            gemm_fused(Y, M, Yn, row_scale=rs, addend=Y, addend_row_scale=es, sym=dev_sym)
             Y, Yn = Yn, Y
             break
-        if sym_inv:
+        if dev_sym:
             spd_inverse_sym(Mi, status, src=M)
         else:
-            spd_inverse_into(M, Mi, status)
+            Mi.copy_(M)
+            spd_inverse(Mi, inplace=True, status=status)
         # Y' = (mu/2) Y + (1/(2 mu)) Y M^-1 ;  M' = I/2 + (mu^2 M + mu^-2 M^-1)/4
         _db_mu_rows(M, Mi, it >= scaled_iters, mu, rs, es)
-        gemm_fused(Y, Mi, Yn, row_scale=rs, addend=Y, addend_row_scale=es, sym=sym_prod)
+        gemm_fused(Y, Mi, Yn, row_scale=rs, addend=Y, addend_row_scale=es, sym=dev_sym)
         Y, Yn = Yn, Y
         if it == 0 and spare is not None:
             # (Yn is S now: the new M goes to the spare buffer; S retires, ws[1] is free)
-            mf_sym(MF_DB, M, Mi, spare, svec=mu, flat=sym_inv and exact_sym)
+            mf_sym(MF_DB, M, Mi, spare, svec=mu, flat=dev_sym and exact_sym)
             M, Yn = spare, ws[1]
             continue
-        mf_sym(MF_DB, M, Mi, Yn, svec=mu, flat=sym_inv and (exact_sym or it > 0))
+        mf_sym(MF_DB, M, Mi, Yn, svec=mu, flat=dev_sym and (exact_sym or it > 0))
         # (Yn was free: the new M went into it)
         M, Yn = Yn, M
     ws[0], ws[1], ws[2], ws[3] = M, Y, Mi, Yn
@@ -648,14 +604,11 @@ def _db_sqrt(S: torch.Tensor, iters: int, scaled_iters: int, status: torch.Tenso
 
 # Denman-Beavers steps: 7 exact steps leave M within 1e-10 of I on production spectra
 # (cond(x^2 + 4x) ~ 1e5 - 7e14, TC on and off; profiles/r06_db_tail.json), the 8th is the
-# Newton-Schulz tail (above; PFML_DB_NS_TAIL=0: an exact 8th step).  The former 9th exact step
+# Newton-Schulz tail (above; ``ns_tail=False``: an exact 8th step).  The former 9th exact step
 # moved nothing (|M - I| ~ 1e-20 .. 1e-32 at its start).  Norm scaling in the first 6.
 DB_ITERS = 8
 DB_SCALED_ITERS = 6
-DB_NS_TAIL = os.environ.get("PFML_DB_NS_TAIL", "1") != "0"
 DB_TAIL_TOL = 1e-7
-# m_tilde_0 by the reference's (sigma_hat - root) / 2 (one pass) instead of the inverse form
-M0_CANCEL = os.environ.get("PFML_M0_CANCEL", "1") != "0"
 nat.register_hip("pfml_db_check", [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                    C.c_double, C.c_void_p, C.c_void_p])
 
@@ -833,7 +786,7 @@ def m_tilde(sigma: torch.Tensor, lam: torch.Tensor, w: torch.Tensor, rf: torch.T
     # sigma_exact_sym: the caller built Sigma exactly symmetric (S4's X F X' in the GEMM's
     # symmetric mode), and the one-triangle inverses keep mt exactly symmetric: the x and
     # fixed-point passes then skip their mirror reads (same bits)
-    flat = sigma_exact_sym and nat.is_device(sigma) and SYM_INVERSE and N >= _BLOCKED_MIN_N
+    flat = sigma_exact_sym and nat.is_device(sigma) and N >= _BLOCKED_MIN_N
     mf_sym(MF_X, sigma, None, x, svec=s, a=a, flat=flat)        # x = s L^-1/2 S L^-1/2
     S = torch.empty_like(sigma)
     four = torch.full((B, N), 4.0, dtype=dt, device=dev)
@@ -851,14 +804,8 @@ def m_tilde(sigma: torch.Tensor, lam: torch.Tensor, w: torch.Tensor, rf: torch.T
     mt = ws[2]
     # (x is exactly symmetric - MF_X symmetrises - and so is root when its last product was
     # the one-triangle one)
-    flat_root = DB_SYMPROD and db_iters > 0 and nat.is_device(x) and N >= _BLOCKED_MIN_N
-    if M0_CANCEL:
-        mf_sym(MF_M0, x, root, mt, d=2.0, flat=flat_root)
-    else:                      # 2 (sigma_hat + root)^-1 (PFML_M0_CANCEL=0: the former form)
-        mf_sym(MF_SHAT, x, root, mt, d=2.0, flat=flat_root)
-        # (an exactly symmetric argument, used symmetrically: the one-triangle form)
-        spd_inverse_sym(mt, status)
-        mt.mul_(2.0)
+    mf_sym(MF_M0, x, root, mt, d=2.0,
+           flat=db_iters > 0 and nat.is_device(x) and N >= _BLOCKED_MIN_N)
     # (the 10 inverses below are of exactly symmetric arguments and only used symmetrically:
     # the one-triangle form)
     Aq = ws[3]

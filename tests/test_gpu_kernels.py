@@ -251,7 +251,7 @@ def test_gemm_sym_and_mirror(gpu, cfg, shape):
     assert torch.equal(Xt.cpu(), X.cpu().transpose(1, 2))
 
 
-@pytest.mark.parametrize("n", [490, 257, 200])
+@pytest.mark.parametrize("n", [490, 257, 200, 160, 193, 321])
 def test_spd_inverse_sym(gpu, n):
     """Symmetric recursive SPD inverse (one-triangle Schur products, mirrored): exactly
     symmetric, and as close to the LU inverse as the two-sided form on a moderately
@@ -272,11 +272,13 @@ def test_spd_inverse_sym(gpu, n):
     assert e_sym < 1e-11 and e_sym < 4 * e_two + 1e-14, (e_sym, e_two)
 
 
-@pytest.mark.parametrize("n", [490, 257, 200])
+@pytest.mark.parametrize("n", [490, 257, 200, 160, 193, 321])
 def test_spd_node_sym_bitwise(gpu, n):
     """The one-launch 65..128-row node (csrc/spd_inverse.hip spd_node_sym_kernel) is bitwise the
     GEMM + leaf launch sequence it replaces (490: nodes of 128 and 106 rows; 257: a 65-row node,
-    m = 1; 200: 128 and 72), including the non-positive-pivot flags."""
+    m = 1; 200: 128 and 72; 160: a full node, then a partial leaf; 193: a 65-row node; 321: a
+    GEMM level above a node and a one-row leaf after one), including the non-positive-pivot
+    flags."""
     import pfml.ops.linalg as la
     g = torch.Generator().manual_seed(n + 1)
     X = torch.randn(6, n + 40, n, generator=g, dtype=torch.float64)
@@ -285,20 +287,16 @@ def test_spd_node_sym_bitwise(gpu, n):
     A[5, n - 3, n - 3] = -50.0                     # not SPD: a pivot of the last node fails
     outs, sts = [], []
     for node in (True, False):
-        la.SYM_NODE = node
-        try:
-            st = torch.zeros(6, dtype=torch.int32, device=gpu)
-            outs.append(la.spd_inverse_sym(A.to(gpu).contiguous(), st).cpu())
-            sts.append(st.cpu())
-        finally:
-            la.SYM_NODE = True
+        st = torch.zeros(6, dtype=torch.int32, device=gpu)
+        outs.append(la.spd_inverse_sym(A.to(gpu).contiguous(), st, node=node).cpu())
+        sts.append(st.cpu())
     assert torch.equal(sts[0], sts[1]) and sts[0].tolist() == [0, 0, 0, 0, 0, 1]
     assert torch.equal(outs[0][:5], outs[1][:5])
     ref = torch.linalg.inv(A[:5])
     assert ((outs[0][:5] - ref).norm(dim=(1, 2)) / ref.norm(dim=(1, 2))).max() < 1e-11
 
 
-@pytest.mark.parametrize("n", [490, 257, 200])
+@pytest.mark.parametrize("n", [490, 257, 200, 160, 193, 321])
 def test_spd_inverse_sym_out_of_place_bitwise(gpu, n):
     """spd_inverse_sym(X, st, src=A) (input only read, no copy) is bitwise the in-place
     inverse of a copy of A, flags included, and leaves A untouched."""

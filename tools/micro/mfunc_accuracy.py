@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Accuracy of the device m_func forms (ops/linalg.py) at the production shape: the
 Denman-Beavers square root vs a symmetric eigendecomposition, and m = diag(a) m_tilde diag(1/a)
-vs the reference-form torch m_func (LU inverses, convergence-checked sqrtm), for the
-Denman-Beavers switches DB_SYM (one-triangle inverse) and DB_SYMPROD (one-triangle Y M^-1).
-Prints one JSON line per arm (max relative errors).
+vs the reference-form torch m_func (LU inverses, convergence-checked sqrtm).  Prints one JSON
+line (max relative errors); the two-sided arms it once compared are recorded in
+profiles/r05_mfunc_db_accuracy.json.
 
     python tools/micro/mfunc_accuracy.py
 """
@@ -38,36 +38,28 @@ def case(B=6, N=496, K=25, n=489, tc=True, seed=1):
 
 def main():
     dev = torch.device("cuda", 0)
-    out = {}
-    refs = {}
+    rec = {}
     for tc in (True, False):
         args, mask = case(tc=tc)
-        refs[tc] = (args, mask, la.m_func_reference(*args, mask=mask))
-    for arm, (dbs, dbp) in {"base": (False, False), "db_sym": (True, False),
-                            "db_symprod": (False, True), "both": (True, True)}.items():
-        la.DB_SYM, la.DB_SYMPROD = dbs, dbp
-        rec = {}
-        for tc, (args, mask, ref) in refs.items():
-            dargs = [x.to(dev) if isinstance(x, torch.Tensor) else x for x in args]
-            mt, a = la.m_tilde(*dargs, mask=mask.to(dev), sigma_exact_sym=False)
-            got = (mt * a.unsqueeze(-1) / a.unsqueeze(-2)).cpu()
-            rec[f"m_rel_tc{int(tc)}"] = float((got - ref).abs().max() / ref.abs().max())
-        # the square root alone vs eigh
-        g = torch.Generator().manual_seed(3)
-        Xs = torch.randn(4, 496, 496, generator=g, dtype=torch.float64)
-        ev = torch.logspace(-6, 0, 496, dtype=torch.float64)
-        Q, _ = torch.linalg.qr(Xs)
-        S = Q @ torch.diag_embed(ev.expand(4, -1)) @ Q.transpose(1, 2)
-        S = 0.5 * (S + S.transpose(1, 2))
-        ref = Q @ torch.diag_embed(ev.sqrt().expand(4, -1)) @ Q.transpose(1, 2)
-        Sd = S.to(dev).contiguous()
-        ws = [torch.empty_like(Sd) for _ in range(4)]
-        st = torch.zeros(4, dtype=torch.int32, device=dev)
-        root = la._db_sqrt(Sd, la.DB_ITERS, la.DB_SCALED_ITERS, st, ws).cpu()
-        rec["sqrt_rel_vs_eigh"] = float((root - ref).abs().max() / ref.abs().max())
-        out[arm] = rec
-        print(json.dumps({arm: rec}), flush=True)
-    print(json.dumps(out))
+        ref = la.m_func_reference(*args, mask=mask)
+        dargs = [x.to(dev) if isinstance(x, torch.Tensor) else x for x in args]
+        mt, a = la.m_tilde(*dargs, mask=mask.to(dev), sigma_exact_sym=False)
+        got = (mt * a.unsqueeze(-1) / a.unsqueeze(-2)).cpu()
+        rec[f"m_rel_tc{int(tc)}"] = float((got - ref).abs().max() / ref.abs().max())
+    # the square root alone vs eigh
+    g = torch.Generator().manual_seed(3)
+    Xs = torch.randn(4, 496, 496, generator=g, dtype=torch.float64)
+    ev = torch.logspace(-6, 0, 496, dtype=torch.float64)
+    Q, _ = torch.linalg.qr(Xs)
+    S = Q @ torch.diag_embed(ev.expand(4, -1)) @ Q.transpose(1, 2)
+    S = 0.5 * (S + S.transpose(1, 2))
+    ref = Q @ torch.diag_embed(ev.sqrt().expand(4, -1)) @ Q.transpose(1, 2)
+    Sd = S.to(dev).contiguous()
+    ws = [torch.empty_like(Sd) for _ in range(4)]
+    st = torch.zeros(4, dtype=torch.int32, device=dev)
+    root = la._db_sqrt(Sd, la.DB_ITERS, la.DB_SCALED_ITERS, st, ws).cpu()
+    rec["sqrt_rel_vs_eigh"] = float((root - ref).abs().max() / ref.abs().max())
+    print(json.dumps(rec))
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Residual max |X A - I| of the batched SPD inverses (ops/linalg.py: one-triangle
-spd_inverse_sym, two-sided spd_inverse_into) over batch sizes up to the S4 production batch,
+spd_inverse_sym, two-sided spd_inverse) over batch sizes up to the S4 production batch,
 with the batch indices of the worst matrices.
 
     python tools/micro/spd_inverse_check.py [n] [B ...]
@@ -30,8 +30,7 @@ def main():
                 X = A.clone()
                 la.spd_inverse_sym(X, st)
             else:
-                X = torch.empty_like(A)
-                la.spd_inverse_into(A, X, st)
+                X = la.spd_inverse(A, status=st)
             r = (torch.bmm(X, A) - eye).abs().amax((1, 2))
             bad = torch.nonzero(r > 1e-10).flatten()
             rec[name] = {"max_res": float(r.max()), "n_bad": int(bad.numel()),
