@@ -6,6 +6,12 @@
 // [T, E] stack and prefix-sums the per-segment totals (53 x E, negligible).  For the 513 x 513
 // denom stack this reads 2.1 MB per month exactly once; rows of even length that are 16-byte
 // aligned take the double2 (16 B per lane) path.
+//
+// The hp-year windows of the grid search follow one canonical chunked association (below).  A
+// rank of a multi-rank run forms them with two kernels around an all-gather of chunk totals
+// (pfml_wsum_chunk_totals, pfml_wsum_chunk_prefix, pfml_wvec_chunk); a one-rank run takes
+// pfml_wsum_onepass, ONE launch that reads every month's upper triangle once and writes the
+// mirrored windows once, bitwise the same.
 #include "common.h"
 
 namespace {
@@ -459,6 +465,274 @@ extern "C" hipError_t pfml_wsum_chunk_prefix(int P, int G, int nseg, int skip, d
   hipLaunchKernelGGL(wsum_chunk_prefix_kernel, dim3(nt * (nt + 1) / 2, G, clast + 1), dim3(256), 0, st, P,
                      nseg, skip, out, scratch, C, cidx, cidx + C, cidx + 2 * C, cidx + 3 * C, tot,
                      tstride, clast);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// One-pass form of the canonical chunked window sums for a rank that owns EVERY chunk (world
+// size one): one launch reads each month's upper triangle once and writes the windows once.
+// No segment sum, chunk total or prefix goes through memory; every element still follows the
+// association of the kernels above exactly (wsum_upper_kernel's four chains per segment,
+// chunk totals folded from 0, E, P_c and the windows as wsum_chunk_prefix_kernel; the vectors
+// as wvec_chunk_kernel), so the bits are those of the two-kernel path.
+//
+// A rank that owns every chunk holds the segments of a chunk side by side and the year
+// chunks' totals fold exactly the segments their windows walk (cs[sy[c]] == ys[c], ce[sy[c]]
+// == ye[c], slot[k] == k: checked by the caller), so one thread can walk its elements' months
+// in canonical order with three running values per element: the prefix P_c, the chunk total
+// and the window.
+//
+// Workgroup (OP_T threads) = one OP_R x OP_C tile of the upper triangle of one g: a thread
+// owns two neighbouring columns of one row (one 16-byte load per month, 8-byte aligned: the
+// row pitch and the month pitch are odd multiples of 8 bytes when P is odd), a half wave
+// reads OP_C * 8 contiguous bytes of a row, and twelve months are in flight per lane, loaded
+// one batch ahead of the adds.  Tiles off the diagonal and off the ragged last column take
+// the unmasked path; the others load element by element and only entries with j >= i.  A
+// window's tile is written straight from the registers and, through LDS, transposed as rows
+// of OP_R doubles (two LDS buffers: one barrier per window).  8 x 64 tiles: every workgroup
+// is resident at once, three per CU at P = 513 (16 x 64 tiles with 512 threads left the CUs
+// one or two workgroups each and the kernel waiting for the CUs with two).  The first
+// ceil(P / OP_VC) workgroups of a g do the vectors.
+namespace {
+constexpr int OP_T = 256, OP_R = 8, OP_C = 64, OP_LD = OP_C + 2;
+constexpr int OP_VC = 32, OP_VRG = OP_T / OP_VC;
+static_assert(OP_T == OP_R * OP_C / 2, "one thread per column pair of the tile");
+static_assert(2 * OP_R * OP_LD <= WV_SEG * OP_VC, "the tile buffers fit the vector job's LDS");
+
+typedef double op_d2 __attribute__((ext_vector_type(2)));
+struct __attribute__((aligned(8))) op_pair { double x, y; };   // 16 bytes, 8-byte aligned
+
+template <bool FULL>
+__device__ __forceinline__ op_d2 op_load(const double* p, bool v0, bool v1) {
+  op_d2 r = {0.0, 0.0};
+  if (FULL) {
+    const op_pair q = *reinterpret_cast<const op_pair*>(p);
+    r.x = q.x;
+    r.y = q.y;
+  } else {
+    if (v0) r.x = p[0];
+    if (v1) r.y = p[1];
+  }
+  return r;
+}
+
+template <bool FULL>
+__device__ __forceinline__ void op_store(double* p, bool v0, bool v1, double x, double y) {
+  if (FULL) {
+    op_pair q = {x, y};
+    *reinterpret_cast<op_pair*>(p) = q;
+  } else {
+    if (v0) p[0] = x;
+    if (v1) p[1] = y;
+  }
+}
+
+// The month stream of one thread: the next batch of up to twelve months of its two elements,
+// loaded one batch ahead of the adds.  The segments are walked in index order (the caller has
+// checked that this IS the canonical order on a rank that owns every chunk), so the batch in
+// ``x`` is always the one the next op_segsum trip consumes; the loads of the batch after it
+// are issued as soon as the adds have freed the registers, before the window is folded,
+// transposed and stored: the memory pipe never drains at a segment boundary.
+template <bool FULL>
+struct OpStream {
+  const double* Xg;                               // X[g] (uniform); off: the thread's (i, j)
+  unsigned off;
+  const int* seg_start;
+  const int* seg_stop;
+  int64_t PP;
+  int nseg, ps, tm, b;
+  bool v0, v1;
+  op_d2 x[12];
+
+  // advance to the next batch and load it: always twelve loads, the months past the end of
+  // the segment clamped to its last month (cache hits, masked at the adds)
+  __device__ __forceinline__ void next() {
+    tm += 12;
+    while (tm >= b && ps < nseg) {
+      tm = seg_start[ps];
+      b = seg_stop[ps];
+      ++ps;
+    }
+    if (tm < b) {
+#pragma unroll
+      for (int m = 0; m < 12; ++m)
+        x[m] = op_load<FULL>(Xg + (int64_t)min(tm + m, b - 1) * PP + off, v0, v1);
+    }
+  }
+
+  // segment sum over months [a, b1): wsum_upper_kernel's order (chain u takes month a + 4 k +
+  // u of the whole groups of four, the leftover months go to chain 0 in month order, then
+  // (c0 + c1) + (c2 + c3)).  A chain is never -0.0 (it starts at +0.0), so the +0.0 of an
+  // absent month leaves its bits alone.
+  __device__ __forceinline__ op_d2 segsum(int a, int b1) {
+    op_d2 c[4] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
+    for (int t0 = a; t0 < b1; t0 += 12) {
+      if (t0 + 12 <= b1) {
+#pragma unroll
+        for (int m = 0; m < 12; ++m) c[m & 3] += x[m];
+      } else {
+        const int n = b1 - t0, n4 = n & ~3;       // months left, of them in whole groups
+#pragma unroll
+        for (int m = 0; m < 8; ++m) c[m & 3] += m < n4 ? x[m] : op_d2{0.0, 0.0};
+#pragma unroll
+        for (int m = 0; m < 11; ++m) c[0] += (m >= n4 && m < n) ? x[m] : op_d2{0.0, 0.0};
+      }
+      next();
+    }
+    return (c[0] + c[1]) + (c[2] + c[3]);
+  }
+};
+
+template <bool FULL>
+__device__ __forceinline__ void op_tile(const double* __restrict__ X, int P, int T, int g, int I,
+                                        int J, const int* __restrict__ seg_start,
+                                        const int* __restrict__ seg_stop, int nseg, int skip,
+                                        const int* __restrict__ cs, const int* __restrict__ ce,
+                                        int C, const int* __restrict__ sb,
+                                        const int* __restrict__ ys, const int* __restrict__ ye,
+                                        int clast, double* __restrict__ SD, double* Ts) {
+  const int64_t PP = (int64_t)P * P;
+  const int nwin = nseg - skip;
+  const int t = threadIdx.x;
+  const int r = t / (OP_C / 2), cp = (t % (OP_C / 2)) * 2;       // tile row, first column
+  const int i = I * OP_R + r, j = J * OP_C + cp;
+  const bool v0 = FULL || (i < P && j < P && j >= i);
+  const bool v1 = FULL || (i < P && j + 1 < P && j + 1 >= i);
+  // the transposed write: target row J OP_C + tc, target columns I OP_R + tr, tr + 1
+  const int tc = t / (OP_R / 2), tr = (t % (OP_R / 2)) * 2;
+  const int i2 = J * OP_C + tc, j2 = I * OP_R + tr;
+  const bool w0 = FULL || (i2 < P && j2 < i2);
+  const bool w1 = FULL || (i2 < P && j2 + 1 < i2);
+  OpStream<FULL> ms;
+  ms.Xg = X + (int64_t)g * T * PP;
+  ms.off = FULL || (i < P && j < P) ? (unsigned)i * P + j : 0u;
+  ms.seg_start = seg_start;
+  ms.seg_stop = seg_stop;
+  ms.PP = PP;
+  ms.nseg = nseg;
+  ms.ps = 0;
+  ms.tm = -12;
+  ms.b = 0;
+  ms.v0 = v0;
+  ms.v1 = v1;
+#pragma unroll
+  for (int m = 0; m < 12; ++m) ms.x[m] = op_d2{0.0, 0.0};
+  ms.next();
+  op_d2 pc = {0.0, 0.0};
+  for (int k = 0; k < C; ++k) {                   // E: the burn-in totals in sb order
+    const int q = sb[k];
+    op_d2 tot = {0.0, 0.0};
+    for (int s = cs[q]; s < ce[q]; ++s) tot += ms.segsum(seg_start[s], seg_stop[s]);
+    pc += tot;
+  }
+  int nst = 0;                                    // windows stored so far: the LDS buffer
+  for (int ch = 0; ch <= clast; ++ch) {
+    op_d2 acc = pc, tot = {0.0, 0.0};
+    for (int s = ys[ch]; s < ye[ch]; ++s) {
+      const op_d2 v = ms.segsum(seg_start[s], seg_stop[s]);
+      tot += v;
+      acc += v;
+      if (s < skip) continue;
+      double* w = SD + ((int64_t)g * nwin + (s - skip)) * PP;
+      op_store<FULL>(w + (int64_t)i * P + j, v0, v1, acc.x, acc.y);
+      double* tb = Ts + (nst & 1) * (OP_R * OP_LD);
+      ++nst;
+      tb[r * OP_LD + cp] = acc.x;
+      tb[r * OP_LD + cp + 1] = acc.y;
+      __syncthreads();
+      op_store<FULL>(w + (int64_t)i2 * P + j2, w0, w1, tb[tr * OP_LD + tc],
+                     tb[(tr + 1) * OP_LD + tc]);
+    }
+    if (ch < clast) pc += tot;
+  }
+}
+
+__global__ __launch_bounds__(OP_T) void wsum_onepass_kernel(
+    const double* __restrict__ X, const double* __restrict__ R, int P, int T,
+    const int* __restrict__ seg_start, const int* __restrict__ seg_stop, int nseg, int skip,
+    const int* __restrict__ cs, const int* __restrict__ ce, int C, const int* __restrict__ sb,
+    const int* __restrict__ ys, const int* __restrict__ ye, int clast, int nvb,
+    double* __restrict__ SD, double* __restrict__ Sr) {
+  __shared__ double smem[WV_SEG * OP_VC];
+  const int g = blockIdx.y, nwin = nseg - skip;
+  if ((int)blockIdx.x >= nvb) {
+    // upper tiles, row by row: tile row I holds the tile columns I OP_R / OP_C .. ntc - 1
+    // (consecutive workgroups, which the dispatcher deals over the XCDs; one run of
+    // consecutive tiles per XCD was measured slower, profiles/r14_experiments.md)
+    int tile = blockIdx.x - nvb;
+    const int ntc = (P + OP_C - 1) / OP_C;
+    int I = 0;
+    while (tile >= ntc - I * OP_R / OP_C) { tile -= ntc - I * OP_R / OP_C; ++I; }
+    const int J = I * OP_R / OP_C + tile;
+    const bool full = I * OP_R + OP_R - 1 <= J * OP_C && J * OP_C + OP_C <= P;
+    if (full)
+      op_tile<true>(X, P, T, g, I, J, seg_start, seg_stop, nseg, skip, cs, ce, C, sb, ys, ye,
+                    clast, SD, smem);
+    else
+      op_tile<false>(X, P, T, g, I, J, seg_start, seg_stop, nseg, skip, cs, ce, C, sb, ys, ye,
+                     clast, SD, smem);
+    return;
+  }
+  // the vectors: segment sums as wvec_chunk_kernel (OP_VRG row groups, eight months in
+  // flight), then its mode 0 and mode 1 folds with the totals kept in a register
+  double (*part)[OP_VC] = reinterpret_cast<double (*)[OP_VC]>(smem);
+  const int lc = threadIdx.x % OP_VC, ry = threadIdx.x / OP_VC;
+  const int col = blockIdx.x * OP_VC + lc;
+  const bool cv = col < P;
+  const double* src = R + (int64_t)g * T * P + (cv ? col : 0);
+  for (int s = ry; s < nseg; s += OP_VRG) {
+    const int a = seg_start[s], b = seg_stop[s];
+    double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int tm = a; tm < b; tm += 8) {
+      double x[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) x[u] = (tm + u < b) ? src[(int64_t)(tm + u) * P] : 0.0;
+#pragma unroll
+      for (int u = 0; u < 8; ++u) acc[u] += x[u];
+    }
+    part[s][lc] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+  }
+  __syncthreads();
+  if (ry != 0 || !cv) return;
+  double pc = 0.0;
+  for (int k = 0; k < C; ++k) {
+    const int q = sb[k];
+    double tot = 0.0;
+    for (int s = cs[q]; s < ce[q]; ++s) tot += part[s][lc];
+    pc += tot;
+  }
+  double* o = Sr + (int64_t)g * nwin * P + col;
+  for (int ch = 0; ch <= clast; ++ch) {
+    double acc = pc, tot = 0.0;
+    for (int s = ys[ch]; s < ye[ch]; ++s) {
+      tot += part[s][lc];
+      acc += part[s][lc];
+      if (s >= skip) o[(int64_t)(s - skip) * P] = acc;
+    }
+    if (ch < clast) pc += tot;
+  }
+}
+
+}  // namespace
+
+// Matrices and vectors in one launch: SD [G, nseg - skip, P, P] (full, mirrored) and Sr [G,
+// nseg - skip, P] from X [G, T, P, P] and R [G, T, P].  idx = [cs, ce, slot] (3 x nlc) and
+// cidx = [sb, sy, ys, ye] (4 x C) as above; the caller has checked that this rank owns every
+// chunk in canonical order (see the kernel's comment).
+extern "C" hipError_t pfml_wsum_onepass(const double* X, const double* R, int P, int T, int G,
+                                        const int* seg_start, const int* seg_stop, int nseg,
+                                        int skip, int nlc, const int* idx, int C, const int* cidx,
+                                        int clast, double* SD, double* Sr, hipStream_t st) {
+  if (nseg <= 0 || P <= 0 || G <= 0 || clast < 0 || nseg - skip <= 0) return hipSuccess;
+  if (nseg > WV_SEG || skip < 0 || T <= 0 || nlc != 2 * C || clast >= C || P > 65535)
+    return hipErrorInvalidValue;
+  const int ntr = (P + OP_R - 1) / OP_R, ntc = (P + OP_C - 1) / OP_C;
+  int ntile = 0;
+  for (int I = 0; I < ntr; ++I) ntile += ntc - I * OP_R / OP_C;
+  const int nvb = (P + OP_VC - 1) / OP_VC;
+  hipLaunchKernelGGL(wsum_onepass_kernel, dim3(nvb + ntile, G), dim3(OP_T), 0, st, X, R, P, T,
+                     seg_start, seg_stop, nseg, skip, idx, idx + nlc, C, cidx, cidx + 2 * C,
+                     cidx + 3 * C, clast, nvb, SD, Sr);
   return hipGetLastError();
 }
 

@@ -26,6 +26,7 @@ all-gather at the end (a few MB; every rank's row count follows from the shared 
 from __future__ import annotations
 
 import ctypes as C
+import os
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -449,11 +450,16 @@ def window_sums(reals: "PfmlReals", su: dict) -> tuple[torch.Tensor, torch.Tenso
     """Expanding-window sums (SD [G, nYl, P, P], Sr [G, nYl, P]) of this rank's hp years in
     the canonical chunk order (see the module docstring): local chunk totals, ONE all-gather
     of them, then the windows.  Device: csrc/segsum.hip (segment sums + totals, windows);
-    CPU: the same folds in torch."""
-    from ..ops.ridge import chunk_totals, chunk_windows
+    CPU: the same folds in torch.  At world size one nothing is exchanged, and the device path
+    is ONE launch that reads every month once and writes the windows once, bitwise the same
+    (``ops.ridge.window_sums_onepass``; ``PFML_WSUM_ONEPASS=0`` keeps the two-kernel path)."""
+    from ..ops.ridge import chunk_totals, chunk_windows, window_sums_onepass
     X, R = reals.denom, reals.r_tilde.contiguous()
-    totD, totR, scratch = chunk_totals(X, R, su)
     env = dist_env()
+    if (X.device.type == "cuda" and R.device.type == "cuda" and env.world_size == 1
+            and not env.is_dist and os.environ.get("PFML_WSUM_ONEPASS", "1") != "0"):
+        return window_sums_onepass(X, R, su)
+    totD, totR, scratch = chunk_totals(X, R, su)
     if env.is_dist:
         # chunk-major rows [slot][matrix totals | vector totals]: ONE known-size all-gather of
         # every rank's chunk totals (matrices and vectors together)

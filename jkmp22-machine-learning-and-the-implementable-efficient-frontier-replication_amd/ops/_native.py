@@ -42,6 +42,8 @@ def _declare_hip(lib):
     lib.pfml_quadform_aligned.restype = I
     lib.pfml_segsum.argtypes = [P, L, P, P, I, P, P]
     lib.pfml_segsum.restype = I
+    lib.pfml_wsum_onepass.argtypes = [P, P, I, I, I, P, P, I, I, I, P, I, P, I, P, P, P]
+    lib.pfml_wsum_onepass.restype = I
     lib.pfml_spd_inverse.argtypes = [P, I, L, L, I, P, P, P]
     lib.pfml_spd_inverse.restype = I
     lib.pfml_spd_inverse_work_doubles.argtypes = [I, I]

@@ -246,6 +246,52 @@ def chunk_windows(X: torch.Tensor, R: torch.Tensor, su: dict, totD: torch.Tensor
     return out, Sr
 
 
+def window_sums_onepass(X: torch.Tensor, R: torch.Tensor, su: dict):
+    """The canonical chunked window sums of a rank that owns every chunk (world size one) in
+    ONE launch (csrc/segsum.hip wsum_onepass_kernel): each month's upper triangle is read once
+    and the windows are written once, with no segment sums or chunk totals in memory.  Bitwise
+    ``chunk_windows(*chunk_totals(...))``.  Returns (SD [G, nYl, P, P], Sr [G, nYl, P])."""
+    G, T, P, _ = X.shape
+    nlc, nseg, skip, nYl, clast = su["nlc"], su["nseg"], su["skip"], su["nYl"], su["clast"]
+    C = su["layout"].C
+    if not nat.is_device(X) or not nat.is_device(R):
+        raise ValueError("window_sums_onepass: device tensors required")
+    if X.dtype != torch.float64 or not X.is_contiguous():
+        raise ValueError("window_sums_onepass: contiguous fp64 required")
+    if R.dtype != torch.float64 or not R.is_contiguous() or R.shape != (G, T, P):
+        raise ValueError("window_sums_onepass: R must be a contiguous fp64 [G, T, P] tensor")
+    if su.get("onepass_T") != T:
+        # the kernel walks each element's months once, in canonical order: every chunk is
+        # local, its total sits in its own slot, a year chunk's total folds the segments of
+        # its windows and the canonical walk visits the segments in index order (checked once
+        # per cached layout)
+        nslot = int(sum(su["counts"]))
+        cs, ce = np.asarray(su["cs"]), np.asarray(su["ce"])
+        sy = np.asarray(su["sy"])[:clast + 1]
+        sb = np.asarray(su["sb"])
+        walk = ([s for k in range(C) if sb[k] < nlc for s in range(cs[sb[k]], ce[sb[k]])]
+                + [s for c in range(clast + 1) for s in range(su["ys"][c], su["ye"][c])])
+        if (nlc != nslot or nlc != 2 * C or nYl != nseg - skip or walk != list(range(nseg))
+                or not np.array_equal(su["slot"], np.arange(nlc))
+                or not np.array_equal(cs[sy], np.asarray(su["ys"])[:clast + 1])
+                or not np.array_equal(ce[sy], np.asarray(su["ye"])[:clast + 1])):
+            raise ValueError("window_sums_onepass: this rank does not own every chunk of the "
+                             "canonical layout (world size one required)")
+        if int(np.max(su["sp"], initial=0)) > T or int(np.min(su["st"], initial=0)) < 0:
+            raise ValueError("window_sums_onepass: window segments out of range")
+        su["onepass_T"] = T
+    SD = torch.empty((G, nYl, P, P), dtype=X.dtype, device=X.device)
+    Sr = torch.empty((G, nYl, P), dtype=X.dtype, device=X.device)
+    if nYl == 0 or nseg == 0:
+        return SD, Sr
+    st, sp, idx, cidx = su["dev_idx"]
+    nat.check(nat.hip_lib().pfml_wsum_onepass(
+        X.data_ptr(), R.data_ptr(), P, T, G, st.data_ptr(), sp.data_ptr(), nseg, skip, nlc,
+        idx.data_ptr(), C, cidx.data_ptr(), clast, SD.data_ptr(), Sr.data_ptr(),
+        nat.stream_of(X)), "pfml_wsum_onepass")
+    return SD, Sr
+
+
 class _HostClock:
     """PFML_HOST_TIMING=1: print host-side section times (microseconds) to stderr;
     PFML_HOST_TIMING=sync: synchronise the device at every mark (section = wall time of the

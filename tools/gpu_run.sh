@@ -23,6 +23,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOT
+# the first kernel of a grid step (one-pass window sums, or the two-kernel path's first kernel)
+STEP_HEAD='wsum_onepass_kernel|wsum_upper_kernel'
 for step in ${MODE//,/ }; do
   case $step in
     peak)
@@ -162,14 +164,15 @@ for step in ${MODE//,/ }; do
       # kernel timeline of the last rank's grid step of a W = 8 rehearsal (graph replay)
       (cd /tmp && export TMPDIR=/tmp PFML_SHARD_GRAPH=1 && timeout -k 10 300 rocprofv3 --kernel-trace -d $OUT/prof8 -o run -- python3 $ROOT/tools/bench_shard.py 8 3 > $OUT/prof8.log 2>&1)
       rc=$?; if [ $rc -ne 0 ]; then tail -3 $OUT/prof8.log; exit $rc; fi
-      python tools/rocprof_timeline.py $(find $OUT/prof8 -name "*.db" | head -1) --last 40 > $OUT/timeline8.txt 2>&1
-      rm -rf $OUT/prof8; tail -34 $OUT/timeline8.txt ;;
+      python tools/rocprof_timeline.py $(find $OUT/prof8 -name "*.db" | head -1) --step-from "$STEP_HEAD" --span "$STEP_HEAD" band_coop_kernel > $OUT/timeline8.txt 2>&1
+      rm -rf $OUT/prof8; cat $OUT/timeline8.txt ;;
     timeline)
-      # kernel timeline of the last full 1-GPU grid step
+      # kernel timeline of the last full 1-GPU grid step, from its first window-sum kernel, and
+      # the front-end span (first window-sum kernel to the first band_coop_kernel) of every step
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace -d $OUT/prof1 -o run -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-inputs > $OUT/prof1.log 2>&1)
       rc=$?; if [ $rc -ne 0 ]; then tail -3 $OUT/prof1.log; exit $rc; fi
-      python tools/rocprof_timeline.py $(find $OUT/prof1 -name "*.db" | head -1) --last 40 > $OUT/timeline1.txt 2>&1
-      tail -32 $OUT/timeline1.txt ;;
+      python tools/rocprof_timeline.py $(find $OUT/prof1 -name "*.db" | head -1) --step-from "$STEP_HEAD" --span "$STEP_HEAD" band_coop_kernel > $OUT/timeline1.txt 2>&1
+      cat $OUT/timeline1.txt ;;
     shards4)
       # per-rank S4 + S5 + S6 of W = 1, 2, 4, 8 rank shards on this GPU (whole-node projection)
       timeout -k 10 900 python tools/bench_shard.py --with-inputs 1,2,4,8 5 > $OUT/shard_s4.json 2> $OUT/shard_s4.err

@@ -53,8 +53,10 @@ def main():
         if m:
             rows.append((m.group(1).strip(), int(m.group(2)), float(m.group(3)),
                          float(m.group(4)), float(m.group(5))))
-    # the last full step: from the last wsum_upper to the last dense_rank
-    i0 = max(i for i, r in enumerate(rows) if r[0].startswith("wsum_upper"))
+    # the last full step: from its first window-sum kernel (the one-pass kernel, or the
+    # two-kernel path's wsum_upper) to the last dense_rank
+    i0 = max(i for i, r in enumerate(rows)
+             if r[0].startswith(("wsum_onepass", "wsum_upper")))
     step = rows[i0:]
     i1 = max(i for i, r in enumerate(step) if r[0].startswith("dense_rank"))
     step = step[:i1 + 1]
@@ -77,7 +79,10 @@ def main():
         return pick[0] if pick else None
     P, T = 513, 710
     wsum_bytes = G * T * P * (P + 1) / 2 * 8
+    win_bytes = G * Y * P * P * 8
     table = [
+        ("wsum_onepass_kernel (window sums, one pass)", dur("wsum_onepass_kernel", True), None,
+         wsum_bytes + win_bytes, "HBM"),
         ("wsum_upper_kernel (window segment sums)", dur("wsum_upper_kernel", True), None, wsum_bytes, "HBM"),
         ("wsum_chunk_totals + prefix (windows)", (dur("wsum_chunk_totals_kernel", True) or 0) + (dur("wsum_chunk_prefix_kernel", True) or 0), None,
          G * 61 * P * (P + 1) / 2 * 8 * 2 + G * Y * P * P * 8, "HBM"),
