@@ -10,6 +10,12 @@ generation and the headline benchmark.
                    (the wealth x gamma efficient frontier -> ef.csv, ef_pf.csv,
                    plots/efficient_frontier.png; needs the prepare-data and estimate-cov
                    outputs only; one process; not part of `main`)
+    python -m pfml pfml-fi      --data-dir Data --device cuda
+                   [--set fi.n_draws=8 --set fi.seed=1 --set fi.clusters=[momentum,value]]
+                   (economic feature importance: Portfolio-ML's realised utility with one
+                   theme of characteristics permuted within every OOS month, per theme and
+                   draw -> fi.csv, fi_pf.csv, plots/feature_importance.png; same inputs as
+                   pfml-ef; one process; not part of `main`)
     python -m pfml stages a,b,c  (several stages in one process)
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m pfml main ...   (RCCL, one rank/GPU)
 

@@ -137,6 +137,9 @@ def _reference_settings() -> dict:
             "scale": True,
         },
         "ef": {"wealth": [1, 1e9, 1e10, 1e11], "gamma_rel": [1, 5, 10, 20, 100]},
+        # feature-theme importance (models/importance.py): permutation draws per theme, the
+        # permutation seed (None: seed_no), the themes (None: every cluster of the labels)
+        "fi": {"n_draws": 1, "seed": None, "clusters": None},
         "cov_set": {
             "industries": True,
             "obs": 252 * 10,
@@ -298,6 +301,11 @@ class Config:
     def hash(self, *sections: str) -> str:
         """Stable hash of (a subset of) the config, used to key stage artifacts."""
         doc = self.to_jsonable()
+        # the whole-config hash keys the stages without a dependency list (and, chained,
+        # everything after them): settings["fi"] is read by pfml-fi alone, which names it, and
+        # stays out, so the keys of every other stage are what they were before it existed
+        if not sections:
+            doc["settings"] = {k: v for k, v in doc["settings"].items() if k != "fi"}
         if sections:
             doc = {s: doc["settings"].get(s, doc["pf_set"].get(s, doc["run"].get(s)))
                    for s in sections}

@@ -24,6 +24,10 @@ CSV_COLUMNS = {
                "r", "sd", "sr_gross", "tc", "r_tc", "sr", "obj", "s4_repairs", "s4_fallbacks",
                "grid_recomputed_cells", "seconds"],
     "ef_pf.csv": ["wealth_end", "gamma_rel", "inv", "shorting", "turnover", "r", "tc", "eom_ret"],
+    "fi.csv": ["cluster", "draw", "n_features", "type", "n", "inv", "shorting",
+               "turnover_notional", "r", "sd", "sr_gross", "tc", "r_tc", "sr", "obj", "obj_drop",
+               "reason"],
+    "fi_pf.csv": ["cluster", "draw", "inv", "shorting", "turnover", "r", "tc", "eom_ret"],
 }
 
 

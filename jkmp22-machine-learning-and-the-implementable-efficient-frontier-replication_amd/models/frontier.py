@@ -178,10 +178,22 @@ def run_point(cfg_pt: Config, chars: pd.DataFrame, barra: BarraCov, wealth_pt: p
     carries what does not depend on the point from one call to the next: the S4 plan (made by
     the first call, ``repoint_s4_plan`` for every point) and the backtest layout.
     ``clock(name)`` is called after each phase (tools/bench_frontier.py)."""
+    c0 = COUNTERS.as_dict()
+    pt = point_inputs(cfg_pt, chars, barra, wealth_pt, risk_free, device, grids, ctx, clock)
+    bt = portfolio.backtest_device(cfg_pt, pt["grid"], pt["res"], ctx["layout"], wealth_pt,
+                                   torch.device(device), keep_weights=keep_weights, clock=clock)
+    bt["diag"] = point_diag(c0, pt)
+    return bt
+
+
+def point_inputs(cfg_pt: Config, chars: pd.DataFrame, barra: BarraCov, wealth_pt: pd.DataFrame,
+                 risk_free: pd.DataFrame, device, grids: dict, ctx: dict, clock=None) -> dict:
+    """Everything of a point in front of its backtest: the (re-aimed) S4 plan, S4 with the OOS
+    months' m_tilde kept, the guarded grid search and the backtest layout (``ctx["layout"]``).
+    Returns {"plan", "res", "grid", "ridge_rep", "ncell"}."""
     tick = clock or (lambda name: None)
     dev = torch.device(device)
     m2, oos = grids["m2"], grids["oos"]
-    c0 = COUNTERS.as_dict()
     if ctx.get("plan") is None:
         ctx["plan"] = pin.make_s4_plan(cfg_pt, chars, barra, wealth_pt, risk_free, dev, m2)
     plan = repoint_s4_plan(ctx["plan"], cfg_pt, wealth_pt)
@@ -203,16 +215,18 @@ def run_point(cfg_pt: Config, chars: pd.DataFrame, barra: BarraCov, wealth_pt: p
         ctx["layout"] = portfolio.backtest_layout(cfg_pt, chars, wealth_pt, oos, m2, res.ids,
                                                   dev, n_pad=plan.N)
         tick("layout")
-    bt = portfolio.backtest_device(cfg_pt, grid, res, ctx["layout"], wealth_pt, dev,
-                                   keep_weights=keep_weights, clock=clock)
+    return {"plan": plan, "res": res, "grid": grid, "ridge_rep": ridge_rep, "ncell": ncell}
+
+
+def point_diag(c0: dict, pt: dict) -> dict:
+    """The diagnostics columns of a point: the fallback counters it moved since ``c0``."""
     c1 = COUNTERS.as_dict()
     fb = {k: v - c0.get(k, 0) for k, v in c1.items() if v != c0.get(k, 0)}
-    if ridge_rep:
-        fb["ridge.repairs"] = int(ridge_rep)
-    bt["diag"] = {"s4_repairs": int(fb.get("pfml_inputs.mfunc_repaired_months", 0)),
-                  "s4_fallbacks": json.dumps(fb, sort_keys=True),
-                  "grid_recomputed_cells": int(ncell)}
-    return bt
+    if pt["ridge_rep"]:
+        fb["ridge.repairs"] = int(pt["ridge_rep"])
+    return {"s4_repairs": int(fb.get("pfml_inputs.mfunc_repaired_months", 0)),
+            "s4_fallbacks": json.dumps(fb, sort_keys=True),
+            "grid_recomputed_cells": int(pt["ncell"])}
 
 
 class _Checkpoint:

@@ -11,7 +11,10 @@
 * ``pf_ts`` / ``pf_summary`` - :220-259, :326-358 (quirks Q3, Q18);
 * ``backtest_layout`` / ``select_hps`` / ``backtest_device`` - the same selection, aims,
                          recursion and statistics from the grid search's tensors with no
-                         DataFrame in between (one frontier point, models/frontier.py);
+                         DataFrame in between (one frontier point, models/frontier.py), with
+                         its pieces ``chosen_coefs`` / ``layout_aims`` / ``layout_m``;
+* ``_chain_multi``     - the recursion for A portfolios sharing m_t (models/importance.py):
+                         every month's m_tilde read once per launch, column k bitwise ``_chain``;
 * ``plots``            - cumulative-performance / hyper-parameter figures (matplotlib).
 """
 from __future__ import annotations
@@ -35,6 +38,9 @@ _P, _I, _L = nat.C.c_void_p, nat.C.c_int, nat.C.c_int64
 nat.register_hip("pfml_weights_chain", [_P, _L, _L, _P, _P, _P, _P, _P, _L, _P, _I, _I, _P, _P,
                                         _P, _P])
 nat.register_hip("pfml_weights_chain_max_n", [])
+nat.register_hip("pfml_weights_chain_multi", [_P, _L, _L, _P, _P, _L, _P, _P, _P, _L, _P, _L, _I,
+                                              _I, _I, _P, _P, _L, _P, _P])
+nat.register_hip("pfml_weights_chain_multi_max_arms", [_I])
 nat.register_hip("pfml_aim_gemv", [_P, _I, _I, _P, _L, _P, _P])
 nat.register_hip("pfml_aim_job_size", [])
 AIM_JOB = np.dtype([("s", "<u8"), ("ld", "<i8"), ("off", "<i8"), ("nrow", "<i4"),
@@ -344,6 +350,57 @@ def _chain(mt_all: torch.Tensor, a_all: torch.Tensor, wa: torch.Tensor, grow: to
     return Wst, Wopt, ws
 
 
+def _chain_multi(mt_all: torch.Tensor, a_all: torch.Tensor, wa: torch.Tensor,
+                 grow: torch.Tensor, nmap_t: torch.Tensor, hit_t: torch.Tensor,
+                 ws0: torch.Tensor):
+    """``_chain`` for A portfolios that share mt_all, a_all, grow, nmap_t and hit_t and differ
+    in their aims wa [A, Bm, N] and, optionally, in ws0 ([A, N]; one [N] serves all):
+    (Wst [A, Bm, N], Wopt [A, Bm, N], w_start after the last month [A, N]).
+
+    Device: csrc/weights.hip weights_month_multi_kernel - one launch per month, every row of
+    m_tilde_t read once for all the portfolios of the launch; A is cut into chunks of at most
+    ``pfml_weights_chain_multi_max_arms(N)``, one chain per chunk on the same stream.  Column k
+    is bitwise ``_chain`` on wa[k].  CPU, or N beyond the kernel's width: one batched matmul
+    per month."""
+    if wa.dim() != 3:
+        raise ValueError("_chain_multi: wa must be [A, Bm, N]")
+    A, Bm, N = wa.shape
+    f64 = dict(dtype=torch.float64, device=wa.device)
+    if ws0.dim() == 2 and ws0.shape[0] != A:
+        raise ValueError("_chain_multi: ws0 must be [N] or [A, N]")
+    Wst = torch.zeros((A, Bm, N), **f64)
+    Wopt = torch.zeros((A, Bm, N), **f64)
+    if nat.is_device(mt_all) and N <= int(nat.hip_lib().pfml_weights_chain_max_n()):
+        ws = torch.empty((A, N), **f64)
+        if not Bm or not A:
+            ws.copy_(ws0.expand(A, N))
+            return Wst, Wopt, ws
+        lib = nat.hip_lib()
+        cap = int(lib.pfml_weights_chain_multi_max_arms(N))
+        if cap < 1:
+            raise RuntimeError(f"pfml_weights_chain_multi takes no portfolio at N = {N}")
+        wa_c, a_c, grow_c = wa.contiguous(), a_all.contiguous(), grow.contiguous()
+        nmap_c, hit_c, ws0_c = nmap_t.contiguous(), hit_t.contiguous(), ws0.contiguous()
+        sws0 = N if ws0_c.dim() == 2 else 0
+        for c0 in range(0, A, cap):
+            Ac = min(cap, A - c0)
+            nat.check(lib.pfml_weights_chain_multi(
+                mt_all.data_ptr(), mt_all.stride(1), mt_all.stride(0), a_c.data_ptr(),
+                wa_c[c0].data_ptr(), Bm * N, grow_c.data_ptr(), nmap_c.data_ptr(),
+                hit_c.data_ptr(), N, ws0_c.data_ptr() + 8 * c0 * sws0, sws0, Bm, N, Ac,
+                Wst[c0].data_ptr(), Wopt[c0].data_ptr(), Bm * N, ws[c0].data_ptr(),
+                nat.stream_of(mt_all)), "pfml_weights_chain_multi")
+        return Wst, Wopt, ws
+    ws = ws0.expand(A, N)
+    for i in range(Bm):
+        Wst[:, i] = ws
+        d = (ws - wa[:, i]) / a_all[i]
+        wopt = wa[:, i] + a_all[i] * torch.matmul(d, mt_all[i].T)
+        Wopt[:, i] = wopt
+        ws = (wopt * grow[i])[:, nmap_t[i]] * hit_t[i]             # next month's w_start
+    return Wst, Wopt, ws.contiguous()
+
+
 def pfml_weights(cfg: Config, chars: pd.DataFrame, barra: BarraCov, wealth: pd.DataFrame,
                  risk_free: pd.DataFrame, aims: pd.DataFrame, oos_months: np.ndarray,
                  device, mine_months: np.ndarray | None = None,
@@ -603,6 +660,71 @@ def select_hps(grid, cfg: Config) -> dict:
     return out
 
 
+def chosen_coefs(cfg: Config, grid, layout: dict, device):
+    """The aim jobs of the OOS months from the selection: (meta, coefs, chosen).  meta[t] = (g,
+    signal position, p, l, year index, p index) of month t; coefs [B, P]: the month's
+    coefficient row (zero beyond p + 1), on ``device``; chosen: {hp year: (g, p, l)} for the
+    years the OOS months draw on."""
+    months = layout["months"]
+    picks = select_hps(grid, cfg)
+    byear = np.asarray(grid.years_local)
+    meta = []                                      # (g, signal position, p, l, year idx, p idx)
+    chosen: dict = {}                              # the hp years the OOS months draw on
+    for t, d in enumerate(months):
+        oos_year = int(month_end(int(d) + 1).year[0])
+        if oos_year - 1 not in picks:
+            raise NoRankedHyperParameters(
+                f"no December rank-1 hyper-parameters for {oos_year - 1}")
+        g, p, l = chosen[oos_year - 1] = picks[oos_year - 1]
+        hit = np.nonzero(byear == oos_year)[0]             # quirk Q13
+        if len(hit) == 0:
+            raise KeyError(f"coefficients of hp year {oos_year} are not on this rank")
+        meta.append((g, int(layout["sig_pos"][t]), p, l, int(hit[0]), cfg.p_vec.index(p)))
+    beta = grid.beta
+    idx = [torch.as_tensor([m[k] for m in meta], device=beta.device) for k in (0, 4, 5, 3)]
+    coefs = beta[idx[0], idx[1], idx[2], idx[3]].contiguous().to(torch.device(device))  # [B, P]
+    return meta, coefs, chosen
+
+
+def layout_aims(sig: list, coefs: torch.Tensor, nk: list, layout: dict, device) -> torch.Tensor:
+    """w_aim = s_t beta of every OOS month in the chain's padded [B, N] layout: sig[t] the
+    month's [n_t, >= nk[t]] signal block, coefs[t, :nk[t]] its coefficients.  Rows without a
+    signal row are NaN (a missing aim), padding columns 0."""
+    dev = torch.device(device)
+    f64 = dict(dtype=torch.float64, device=dev)
+    N, B = layout["N"], layout["B"]
+    nsig = np.asarray([int(x.shape[0]) for x in sig], np.int64)
+    direct = layout["sig_identity"]
+    Na = N if direct else max(int(nsig.max()) if B else 1, 1)
+    wa = torch.zeros((B, Na), **f64)
+    if B and dev.type == "cuda" and all(x.is_cuda and x.stride(-1) == 1 for x in sig):
+        _aim_gemv(sig, coefs, nk, np.arange(B, dtype=np.int64) * Na, wa)
+    else:
+        for t, s_ in enumerate(sig):
+            wa[t, : s_.shape[0]] = (s_[:, : nk[t]] @ coefs[t, : nk[t]].to(s_.device)).to(dev)
+    if not direct:                                 # signal rows -> the month's valid rows
+        sm = layout["smap"]
+        wa = torch.where(sm >= 0, wa.gather(1, sm.clamp(min=0)),
+                         torch.full((), float("nan"), **f64))
+        wa = torch.where(layout["live"], wa, torch.zeros((), **f64))
+    return wa
+
+
+def layout_m(inputs, layout: dict, device):
+    """S4's kept m_tilde and a of the layout's months: (mt_all [B, N, N] view, a_all [B, N])."""
+    months, ns, N = layout["months"], layout["ns"], layout["N"]
+    kpos = m_cache_positions(inputs.m_keep, months, ns, layout["ids"], N, torch.device(device))
+    if kpos is None:
+        raise RuntimeError("backtest_device needs S4's m_tilde of every OOS month "
+                           "(build_inputs(..., keep_m=oos months), fp64, same device)")
+    mk = inputs.m_keep
+    if len(kpos) == mk["mt"].shape[0] and bool((kpos == torch.arange(len(kpos),
+                                                                     device=kpos.device)).all()):
+        return mk["mt"][:, :N, :N], mk["a"][:, :N].contiguous()
+    return (mk["mt"].index_select(0, kpos)[:, :N, :N],
+            mk["a"].index_select(0, kpos)[:, :N].contiguous())
+
+
 def backtest_device(cfg: Config, grid, inputs, layout: dict, wealth: pd.DataFrame, device,
                     keep_weights: bool = False, clock=None) -> dict:
     """S6 selection -> S7 aims -> S9 recursion -> per-month statistics with no DataFrame in
@@ -621,56 +743,16 @@ def backtest_device(cfg: Config, grid, inputs, layout: dict, wealth: pd.DataFram
     dev = torch.device(device)
     f64 = dict(dtype=torch.float64, device=dev)
     months, ns, N, B = layout["months"], layout["ns"], layout["N"], layout["B"]
-    picks = select_hps(grid, cfg)
+    meta, coefs, chosen = chosen_coefs(cfg, grid, layout, dev)
     tick("selection")
 
     # ---- aims of the chosen (g, month) jobs only, into the chain's padded layout -------
-    byear = np.asarray(grid.years_local)
-    meta = []                                      # (g, signal position, p, l, year idx, p idx)
-    chosen: dict = {}                              # the hp years the OOS months draw on
-    for t, d in enumerate(months):
-        oos_year = int(month_end(int(d) + 1).year[0])
-        if oos_year - 1 not in picks:
-            raise NoRankedHyperParameters(
-                f"no December rank-1 hyper-parameters for {oos_year - 1}")
-        g, p, l = chosen[oos_year - 1] = picks[oos_year - 1]
-        hit = np.nonzero(byear == oos_year)[0]             # quirk Q13
-        if len(hit) == 0:
-            raise KeyError(f"coefficients of hp year {oos_year} are not on this rank")
-        meta.append((g, int(layout["sig_pos"][t]), p, l, int(hit[0]), cfg.p_vec.index(p)))
-    beta = grid.beta
-    idx = [torch.as_tensor([m[k] for m in meta], device=beta.device) for k in (0, 4, 5, 3)]
-    coefs = beta[idx[0], idx[1], idx[2], idx[3]].contiguous().to(dev)    # [B, P]
     sig = [inputs.signal_t[m[0]][m[1]] for m in meta]
-    nsig = np.asarray([int(x.shape[0]) for x in sig], np.int64)
-    direct = layout["sig_identity"]
-    Na = N if direct else max(int(nsig.max()) if B else 1, 1)
-    wa = torch.zeros((B, Na), **f64)
-    if B and dev.type == "cuda" and all(x.is_cuda and x.stride(-1) == 1 for x in sig):
-        _aim_gemv(sig, coefs, [m[2] + 1 for m in meta], np.arange(B, dtype=np.int64) * Na, wa)
-    else:
-        for t, (s_, m) in enumerate(zip(sig, meta)):
-            wa[t, : s_.shape[0]] = (s_[:, : m[2] + 1] @ coefs[t, : m[2] + 1].to(s_.device)).to(dev)
-    if not direct:                                 # signal rows -> the month's valid rows
-        sm = layout["smap"]
-        wa = torch.where(sm >= 0, wa.gather(1, sm.clamp(min=0)),
-                         torch.full((), float("nan"), **f64))
-        wa = torch.where(layout["live"], wa, torch.zeros((), **f64))
-
+    wa = layout_aims(sig, coefs, [m[2] + 1 for m in meta], layout, dev)
     tick("aims")
 
     # ---- m_t from S4, the chain, the statistics ----------------------------------------
-    kpos = m_cache_positions(inputs.m_keep, months, ns, layout["ids"], N, dev)
-    if kpos is None:
-        raise RuntimeError("backtest_device needs S4's m_tilde of every OOS month "
-                           "(build_inputs(..., keep_m=oos months), fp64, same device)")
-    mk = inputs.m_keep
-    if len(kpos) == mk["mt"].shape[0] and bool((kpos == torch.arange(len(kpos),
-                                                                     device=kpos.device)).all()):
-        mt_all, a_all = mk["mt"][:, :N, :N], mk["a"][:, :N].contiguous()
-    else:
-        mt_all = mk["mt"].index_select(0, kpos)[:, :N, :N]
-        a_all = mk["a"].index_select(0, kpos)[:, :N].contiguous()
+    mt_all, a_all = layout_m(inputs, layout, dev)
     args = (wa, layout["grow"], layout["nmap"], layout["hit"], layout["ws0"])
     Wst, Wopt, _ = _chain(mt_all, a_all, *args)
     # failure detection as in the pfml-best-hps stage: a non-finite w_start means a fault in

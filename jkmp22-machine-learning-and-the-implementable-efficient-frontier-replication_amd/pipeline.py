@@ -13,6 +13,7 @@ Stages (CLI names) and the reference script each one replaces:
     pfml-aim             PFML_aim_fun.py
     pfml-hps             PFML_hps.py
     pfml-best-hps        PFML_best_hps.py
+    pfml-fi              (none: feature-theme importance, settings["fi"]; not in ``main``)
     pfml-ef              (none: the wealth x gamma frontier of settings["ef"]; not in ``main``)
 
 State flows in memory within one process; with ``checkpoint=True`` every stage also writes
@@ -59,7 +60,7 @@ log = get_logger("pipeline")
 
 MAIN_STAGES = ["prepare-data", "estimate-cov", "pfml-input", "pfml-search-coef",
                "pfml-hp-reals", "pfml-aim", "pfml-hps", "pfml-best-hps"]
-ALL_STAGES = ["get-additional-data", "sp500-subset"] + MAIN_STAGES + ["pfml-ef"]
+ALL_STAGES = ["get-additional-data", "sp500-subset"] + MAIN_STAGES + ["pfml-fi", "pfml-ef"]
 
 # settings sections (and run options) each stage's output depends on (for resume keys);
 # keys chain, so a change invalidates the stage and everything downstream
@@ -77,7 +78,14 @@ _DEPS = {
     # the frontier re-runs S4-S9 per point from the prepare-data / estimate-cov outputs
     "pfml-ef": ("ef", "pf_ml", "Transaction_Costs", "seed_no", "compat_mode", "precision",
                 "iterations", "pf", "mu", "lb_hor"),
+    # feature importance: one such point plus the permuted arms (models/importance.py)
+    "pfml-fi": ("fi", "pf_ml", "Transaction_Costs", "seed_no", "compat_mode", "precision",
+                "iterations", "pf", "mu", "lb_hor"),
 }
+# stages outside the key chain: a sibling's key is its parent's chained key plus its own
+# dependency hash, and the chain runs on without it (pfml-fi was added in front of pfml-ef,
+# whose key - and with it every frontier checkpoint - stays what it was)
+_SIBLING_OF = {"pfml-fi": "pfml-best-hps"}
 # stages whose artifacts are per rank (resume per shard)
 _SHARDED = ("pfml-input", "pfml-search-coef")
 # per-rank artifact payload versions (part of the done-marker key)
@@ -96,8 +104,12 @@ class Pipeline:
         self._keys = {}
         key = ""
         for st in ALL_STAGES:
+            if st in _SIBLING_OF:
+                continue
             key = key + "|" + self.cfg.hash(*_DEPS.get(st, ())) + st
             self._keys[st] = key
+        for st, parent in _SIBLING_OF.items():
+            self._keys[st] = self._keys[parent] + "|" + self.cfg.hash(*_DEPS[st]) + st
 
     # ---------------------------------------------------------------------------------
     def run(self, stages: list[str] | None = None) -> dict:
@@ -477,3 +489,25 @@ class Pipeline:
             frontier.plot_frontier(out["ef"], os.path.join(d, "plots"))
         log.info("efficient frontier:\n" + out["ef"][["wealth_end", "gamma_rel", "r", "sd",
                                                       "tc", "r_tc", "obj"]].to_string(index=False))
+
+    def _pfml_fi(self):
+        """Feature-theme importance (models/importance.py): the benchmark point at the
+        configured wealth and gamma plus one counterfactual portfolio per (theme, draw) of
+        settings["fi"], from the prepare-data and estimate-cov outputs alone."""
+        from .models import importance
+        if self.env.world_size > 1:
+            raise RuntimeError(importance.WORLD_ERROR)
+        self._load_common()
+        st = self.state
+        d = self.cfg.run.data_dir
+        labels = pd.read_csv(io.path(d, "cluster_labels_processed.csv"))
+        out = importance.feature_importance(self.cfg, st["chars"], st["barra"], st["wealth"],
+                                            st["risk_free"], labels, self.device)
+        io.write_csv(out["fi"], d, "fi.csv")
+        io.write_csv(out["pf"], d, "fi_pf.csv")
+        st.update(fi=out["fi"], fi_pf=out["pf"])
+        if self.cfg.run.plots:
+            importance.plot_importance(out["fi"], os.path.join(d, "plots"))
+        log.info("feature importance:\n" + out["fi"][["cluster", "draw", "n_features", "r", "sd",
+                                                       "tc", "obj", "obj_drop"]]
+                 .to_string(index=False))
