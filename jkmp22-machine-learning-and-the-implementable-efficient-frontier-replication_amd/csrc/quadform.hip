@@ -18,8 +18,11 @@
 // Tile: 64 rows of D x 112 lambda columns (L <= 112) of one job per 256-thread workgroup (3
 // per CU); each wave owns 16 rows x 7 MFMA 16x16 accumulators.  Every workgroup writes a
 // deterministic per-row-tile partial; a second tiny kernel sums the partials in a fixed order
-// (bitwise reproducible, no float atomics).  The host lists the tiles longest-first
-// (tile_job[tile] = job << 5 | row tile, ops/ridge.py quad_plan).
+// (bitwise reproducible, no float atomics).  The host lists the tiles
+// (tile_job[tile] = job << 5 | row tile, ops/ridge.py quad_plan) longest-first, and by
+// default cuts them into runs - one cell's one row tile over consecutive validation months,
+// levelled to about 64 K steps - which one workgroup of the pipelined kernel walks back to
+// back (run_off; quad_pipe_body below).
 //
 // D_t is symmetric:  b'Db = sum_I b_I'(D_II b_I + 2 sum_{K>I} D_IK b_K).  A row tile I only
 // walks K >= I, with the diagonal block weighted 1/2, so  acc = U_I / 2  and half the flops
@@ -29,9 +32,11 @@
 //  * quadform_pipe_kernel (default): the direct-A form below with a software-pipelined K
 //    loop for aligned tiles (main index count a multiple of 64: every production cell) -
 //    no branch, clamp or select around a load, counted vmcnt / lgkmcnt waits only, two B
-//    fragment register sets, no vector ALU work beside the 28 MFMAs of a step, and an
-//    epilogue whose loads go out in one batch.  Tiles that are not aligned go to
-//    quadform_rest_kernel, the direct form's loop, in a second launch.
+//    fragment register sets, no vector ALU work beside the 28 MFMAs of a step, an
+//    epilogue whose loads go out in two batches, and the pipeline kept full from one tile of
+//    a run to the next (pfml_quadform_runs; pfml_quadform: every tile a run of its own).
+//    Tiles that are not aligned go to quadform_rest_kernel, the direct form's loop, one per
+//    workgroup in a second launch.
 //  * quadform_direct_kernel (PFML_QUAD_DIRECT=1): the direct-A form for every tile.
 // The pipelined and the direct form add the same products in the same order (the diagonal
 // block's weight 1/2 is a power of two wherever it is applied), so barring underflow they
@@ -92,12 +97,11 @@ __host__ __device__ __forceinline__ bool quad_aligned(int nfull, int L, int64_t 
          (int64_t)L * ldB * 8 < (int64_t(1) << 31);
 }
 
-// One body, three kernels.  QD_ALL: the direct form's loop for every tile.  QD_PIPE: the
-// pipelined loop for the aligned tiles of the launch, any other tile is left alone.
-// QD_REST: the direct form's loop for exactly the tiles QD_PIPE leaves (launched after it,
-// and only when the host's plan holds such a tile).  A tile's arithmetic depends on its own
-// job alone, so results do not depend on what else the launch holds.
-enum { QD_ALL = 0, QD_PIPE = 1, QD_REST = 2 };
+// The direct form's loop, one tile per workgroup, in two kernels.  QD_ALL: every tile.
+// QD_REST: exactly the tiles the pipelined kernel leaves (launched after it, and only when
+// the host's plan holds such a tile).  A tile's arithmetic depends on its own job alone, so
+// results do not depend on what else the launch holds.
+enum { QD_ALL = 0, QD_REST = 2 };
 
 template <int MODE>
 __device__ __forceinline__ void quad_direct_body(
@@ -153,130 +157,9 @@ __device__ __forceinline__ void quad_direct_body(
   };
 
   const int nst = (n - i0 + BK - 1) / BK;          // K steps of this row tile
-  if constexpr (MODE != QD_ALL) {
-    if (quad_aligned(nfull, L, ldD, ldB) != (MODE == QD_PIPE)) return;   // not this kernel's
+  if constexpr (MODE == QD_REST) {
+    if (quad_aligned(nfull, L, ldD, ldB)) return;    // the pipelined kernel's
   }
-  if constexpr (MODE == QD_PIPE) {
-    // Pipelined loop (nst is a multiple of 4, >= 4).  No clamp, select or branch sits around
-    // a load: D and beta come through one buffer resource each, a loop-invariant 32-bit
-    // offset per element in a VGPR and the step's k offset in an SGPR, clamped to the last
-    // K tile - the two steps past the end load that tile again and nobody reads it.  The
-    // D ring has four slots so that slot and LDS buffer are compile-time constants of a
-    // loop unrolled by four; D is loaded two steps ahead, after the next step's beta, so
-    // the counted wait for beta at the end of a step leaves it in flight.  The B fragments
-    // of a k-slice sit in one of two register sets: slice s + 1 is read from LDS while
-    // slice s's MFMAs issue.  The diagonal block's weight 1/2 is applied to the accumulators
-    // once, after the block's four steps (exact: a power of two).
-    const int dbytes = (int)(((int64_t)(nfull - 1) * ldD + nfull) * 8);
-    const int bbytes = (int)(((int64_t)(L - 1) * ldB + nfull) * 8);
-    const __amdgpu_buffer_rsrc_t rsD =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(Dm), 0, dbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(bt), 0, bbytes, 0x00020000);
-    const int dvo = ((i0 + w * 16 + r) * (int)ldD + 4 * c) * 8;
-    int bvo[BQ];
-#pragma unroll
-    for (int q = 0; q < BQ; ++q) bvo[q] = (min((t >> 4) + 16 * q, L - 1) * (int)ldB + (t & 15)) * 8;
-    // LDS element of this thread's staged beta (row t / 16 + 16 q: same swizzle for every
-    // q) and of its fragment of slice s (row 16 q + r); both + 256 q
-    const int bso = (t >> 4) * BK + ((t & 15) ^ qd_swz(t >> 4));
-    int fro[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) fro[s] = r * BK + ((4 * c + s) ^ swz);
-    const int klast = (n - BK) * 8;                // byte offset of the last K tile
-    double fa[4][4], fr[BQ];
-    auto fdload = [&](int slot, int kb) {
-      const double2_t lo = __builtin_bit_cast(
-          double2_t, __builtin_amdgcn_raw_buffer_load_b128(rsD, dvo, kb, 0));
-      const double2_t hi = __builtin_bit_cast(
-          double2_t, __builtin_amdgcn_raw_buffer_load_b128(rsD, dvo + 16, kb, 0));
-      fa[slot][0] = lo[0]; fa[slot][1] = lo[1]; fa[slot][2] = hi[0]; fa[slot][3] = hi[1];
-    };
-    auto fbload = [&](int kb) {
-#pragma unroll
-      for (int q = 0; q < BQ; ++q)
-        fr[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rsB, bvo[q], kb, 0));
-    };
-    auto fbstore = [&](int buf) {
-#pragma unroll
-      for (int q = 0; q < BQ; ++q) Bs[buf][q * 256 + bso] = fr[q];
-    };
-    auto fstep = [&](auto slot_c, int kb) {
-      constexpr int cur = decltype(slot_c)::value;
-      constexpr int buf = cur & 1;
-      fbload(min(kb + BK * 8, klast));
-      fdload((cur + 2) & 3, min(kb + 2 * BK * 8, klast));
-      double fb[2][NTILE];
-#pragma unroll
-      for (int q = 0; q < NTILE; ++q) fb[0][q] = Bs[buf][q * 256 + fro[0]];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        if (s < 3) {
-#pragma unroll
-          for (int q = 0; q < NTILE; ++q) fb[(s + 1) & 1][q] = Bs[buf][q * 256 + fro[s + 1]];
-        }
-#pragma unroll
-        for (int q = 0; q < NTILE; ++q) acc[q] = mfma_f64_16x16x4(fa[cur][s], fb[s & 1][q], acc[q]);
-      }
-      fbstore(buf ^ 1);
-      __syncthreads();
-    };
-    const int kb0 = i0 * 8, kend = n * 8;
-    fbload(kb0);
-    fdload(0, kb0);
-    fdload(1, kb0 + BK * 8);
-    fbstore(0);
-    __syncthreads();
-    // every step stages and syncs, the last one included (it stages the clamped tile for
-    // nobody): with the last step's staging under a branch the compiler sinks its beta loads
-    // into that branch and waits for them there in full, once per four steps
-    for (int kb = kb0; kb < kend; kb += 4 * BK * 8) {
-      fstep(std::integral_constant<int, 0>{}, kb);
-      fstep(std::integral_constant<int, 1>{}, kb + BK * 8);
-      fstep(std::integral_constant<int, 2>{}, kb + 2 * BK * 8);
-      fstep(std::integral_constant<int, 3>{}, kb + 3 * BK * 8);
-      if (kb == kb0) {
-#pragma unroll
-        for (int q = 0; q < NTILE; ++q) acc[q] *= 0.5;
-      }
-    }
-    __syncthreads();                               // red reuses Bs
-    // Tail column and epilogue as below, but every row is in range here, so all their
-    // loads (r_i, beta_l[i], beta_l[n], D[i][n]) are issued unconditionally in one batch
-    // (under `if (gi < n && l < L)` each of the 28 products waited for its own loads: 28
-    // memory round trips in a row, more than the whole K loop of a 4-step tile).  Columns
-    // l >= L compute on row L - 1's beta; nobody reads their sums.
-    auto grow = [&](int rr) { return i0 + w * 16 + PFML_F64_CROW(lane, rr); };
-    const int tn = (tail ? n : n - 1) * 8;         // in range either way; used if tail
-    double er[4], td[4], eb[NTILE][4], tb[NTILE];
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      er[rr] = rm[grow(rr)];
-      td[rr] = __builtin_bit_cast(
-          double, __builtin_amdgcn_raw_buffer_load_b64(rsD, grow(rr) * (int)ldD * 8, tn, 0));
-    }
-#pragma unroll
-    for (int q = 0; q < NTILE; ++q) {
-      const int lo = min(q * 16 + r, L - 1) * (int)ldB * 8;
-      tb[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rsB, lo, tn, 0));
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr)
-        eb[q][rr] = __builtin_bit_cast(
-            double, __builtin_amdgcn_raw_buffer_load_b64(rsB, lo + grow(rr) * 8, 0, 0));
-    }
-#pragma unroll
-    for (int q = 0; q < NTILE; ++q) {
-      double s = 0.0;
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const double u = tail ? fma(td[rr], tb[q], acc[q][rr]) : acc[q][rr];
-        s += eb[q][rr] * (er[rr] - u);               // u = U / 2
-      }
-      s += __shfl_xor(s, 16, 64);
-      s += __shfl_xor(s, 32, 64);
-      if (lane < 16) red[w][q * 16 + r] = s;
-    }
-  } else {
   bload(i0);
   dload(0, i0);
   if (nst > 1) dload(1, i0 + BK);
@@ -342,13 +225,239 @@ __device__ __forceinline__ void quad_direct_body(
     s += __shfl_xor(s, 32, 64);
     if (lane < 16) red[w][l] = s;
   }
-  }
   __syncthreads();
   if (t < L) {
     double s = 0.0;
 #pragma unroll
     for (int q = 0; q < NW; ++q) s += red[q][t];
     partial[(int64_t)(jd.ptile0 + rt) * L + t] = s;
+  }
+}
+
+// Pipelined form for aligned tiles.  A workgroup walks a *run* of tiles back to back: entries
+// tile_job[run_off[b] .. run_off[b + 1]) of the launch's tile list, which the host fills with
+// one cell's one row tile over consecutive validation months (ops/ridge.py quad_plan), or,
+// without a run table (run_off == nullptr), the single tile tile_job[b] - a run of one, and
+// exactly the one-tile-per-workgroup kernel this replaced.  The months of a run share the beta
+// block, the K range, the tile shape and the epilogue's beta rows; only D_t, r_t and the
+// partial slot change.  So the row tile, n, the beta base and every loop-invariant offset are
+// set up once per run, the next month's D base is fetched a month ahead, and the pipeline
+// never drains at a month boundary: the last two steps of month t load the first two D
+// fragments of month t + 1, the last step stages beta's first K tile again (it wraps), and
+// r_t and the tail column of D_t are requested at the head of the month's last four steps.  A
+// boundary then costs the epilogue alone (two batches of L2-resident beta loads, the sums,
+// two barriers), not a descriptor fetch, a cold D / beta fetch and a ring fill.  Every month has
+// an accumulator set and a partial slot of its own, with the products added in the order of
+// the one-tile kernel: results are bitwise the same whatever the runs are.
+//
+// K loop (nst is a multiple of 4, >= 4).  No clamp, select or branch sits around a load: D
+// and beta come through one buffer resource each, a loop-invariant 32-bit offset per element
+// in a VGPR and the step's k offset in an SGPR.  The D ring has four slots so that slot and
+// LDS buffer are compile-time constants of a loop unrolled by four; D is loaded two steps
+// ahead, after the next step's beta, so the counted wait for beta at the end of a step leaves
+// it in flight.  The last four steps of a month are peeled: they alone look past the month's
+// end (after a run's last month they load the last K tile again and beta's first, for
+// nobody).  The B fragments of a k-slice sit in one of two register sets: slice s + 1 is read
+// from LDS while slice s's MFMAs issue.  The diagonal block's weight 1/2 is applied to the
+// accumulators once, after the block's four steps (exact: a power of two).  Every step stages
+// and syncs, the last one included: with the last step's staging under a branch the compiler
+// sinks its beta loads into that branch and waits for them there in full.
+__device__ __forceinline__ void quad_pipe_body(
+    double (*Bs)[NCOL * BK], const double* __restrict__ D, int64_t ldD,
+    const double* __restrict__ R, const double* __restrict__ Bt, int64_t ldB,
+    const JobDesc* __restrict__ jobs, const int* __restrict__ tile_job,
+    const int* __restrict__ run_off, int L, double* __restrict__ partial) {
+  static_assert(NW * NCOL <= NCOL * BK, "cross-wave sums must fit in one beta buffer");
+  // the sums go through buffer 1: at a month boundary buffer 0 already holds the next
+  // month's first beta tile
+  double (*red)[NCOL] = reinterpret_cast<double (*)[NCOL]>(&Bs[1][0]);
+
+  int first = blockIdx.x, last = first + 1;
+  if (run_off) {
+    first = run_off[blockIdx.x];
+    last = run_off[blockIdx.x + 1];
+  }
+  if (first >= last) return;
+  const int tj = tile_job[first];
+  const int rt = tj & 31;
+  JobDesc jd = jobs[tj >> 5];
+  const int i0 = rt * BM;
+  const int nfull = jd.n;
+  const int n = quad_main(nfull);
+  const bool tail = n != nfull;
+  if (!quad_aligned(nfull, L, ldD, ldB) || i0 >= n) return;   // quadform_rest_kernel's
+  const double* bt = Bt + jd.b_off;
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int r = lane & 15, c = lane >> 4;
+  const int swz = qd_swz(r);                      // g(16 q + r) = g(r)
+  constexpr int BQ = (NCOL * BK) / NT;             // 7 beta elements per thread per step
+
+  const int dbytes = (int)(((int64_t)(nfull - 1) * ldD + nfull) * 8);
+  const int bbytes = (int)(((int64_t)(L - 1) * ldB + nfull) * 8);
+  auto d_rsrc = [&](int64_t d_off) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(D + d_off), 0, dbytes,
+                                             0x00020000);
+  };
+  __amdgpu_buffer_rsrc_t rsD = d_rsrc(jd.d_off);
+  const __amdgpu_buffer_rsrc_t rsB =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(bt), 0, bbytes, 0x00020000);
+  const int dvo = ((i0 + w * 16 + r) * (int)ldD + 4 * c) * 8;
+  int bvo[BQ];
+#pragma unroll
+  for (int q = 0; q < BQ; ++q) bvo[q] = (min((t >> 4) + 16 * q, L - 1) * (int)ldB + (t & 15)) * 8;
+  // LDS element of this thread's staged beta (row t / 16 + 16 q: same swizzle for every
+  // q) and of its fragment of slice s (row 16 q + r); both + 256 q
+  const int bso = (t >> 4) * BK + ((t & 15) ^ qd_swz(t >> 4));
+  int fro[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) fro[s] = r * BK + ((4 * c + s) ^ swz);
+  constexpr int S = BK * 8;                        // bytes of a K step along a row
+  const int klast = (n - BK) * 8;                  // byte offset of the last K tile
+  double fa[4][4], fr[BQ];
+  auto fdload = [&](__amdgpu_buffer_rsrc_t rs, int slot, int kb) {
+    const double2_t lo = __builtin_bit_cast(
+        double2_t, __builtin_amdgcn_raw_buffer_load_b128(rs, dvo, kb, 0));
+    const double2_t hi = __builtin_bit_cast(
+        double2_t, __builtin_amdgcn_raw_buffer_load_b128(rs, dvo + 16, kb, 0));
+    fa[slot][0] = lo[0]; fa[slot][1] = lo[1]; fa[slot][2] = hi[0]; fa[slot][3] = hi[1];
+  };
+  auto fbload = [&](int kb) {
+#pragma unroll
+    for (int q = 0; q < BQ; ++q)
+      fr[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rsB, bvo[q], kb, 0));
+  };
+  auto fbstore = [&](int buf) {
+#pragma unroll
+    for (int q = 0; q < BQ; ++q) Bs[buf][q * 256 + bso] = fr[q];
+  };
+  double4_t acc[NTILE];
+  // one K step on D slot `cur`: beta of the next step (byte offset kbn) first, then D two
+  // steps ahead (resource rs, byte offset kdn), then whatever else the caller has to request
+  auto fstep = [&](auto slot_c, int kbn, __amdgpu_buffer_rsrc_t rs, int kdn, auto&& also) {
+    constexpr int cur = decltype(slot_c)::value;
+    constexpr int buf = cur & 1;
+    fbload(kbn);
+    fdload(rs, (cur + 2) & 3, kdn);
+    also();
+    double fb[2][NTILE];
+#pragma unroll
+    for (int q = 0; q < NTILE; ++q) fb[0][q] = Bs[buf][q * 256 + fro[0]];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      if (s < 3) {
+#pragma unroll
+        for (int q = 0; q < NTILE; ++q) fb[(s + 1) & 1][q] = Bs[buf][q * 256 + fro[s + 1]];
+      }
+#pragma unroll
+      for (int q = 0; q < NTILE; ++q) acc[q] = mfma_f64_16x16x4(fa[cur][s], fb[s & 1][q], acc[q]);
+    }
+    fbstore(buf ^ 1);
+    __syncthreads();
+  };
+  auto nothing = [] {};
+  const std::integral_constant<int, 0> s0{};
+  const std::integral_constant<int, 1> s1{};
+  const std::integral_constant<int, 2> s2{};
+  const std::integral_constant<int, 3> s3{};
+  const int tn = (tail ? n : n - 1) * 8;           // in range either way; used if tail
+
+  const int kb0 = i0 * 8, kend = n * 8;
+  fbload(kb0);
+  fdload(rsD, 0, kb0);
+  fdload(rsD, 1, kb0 + S);
+  fbstore(0);
+  __syncthreads();
+  for (int m = first;; ++m) {
+    // the next month of the run: its D base, and where the last two steps look ahead to
+    const bool more = m + 1 < last;
+    JobDesc jn = jd;
+    if (more) jn = jobs[tile_job[m + 1] >> 5];
+    const __amdgpu_buffer_rsrc_t rsN = d_rsrc(jn.d_off);
+    const int nk0 = more ? kb0 : klast, nk1 = more ? kb0 + S : klast;
+    const double* rm = R + jd.r_off;
+#pragma unroll
+    for (int q = 0; q < NTILE; ++q) acc[q] = double4_t{0.0, 0.0, 0.0, 0.0};
+    // The epilogue's ~20 loop-invariant load offsets are rebuilt every month from these two
+    // (opaque to the compiler here): hoisted out of the month loop they would sit in VGPRs
+    // through every K loop and push the kernel past three waves per SIMD.
+    int er_ = r, eg_ = i0 + w * 16 + PFML_F64_CROW(lane, 0);
+    asm volatile("" : "+v"(er_), "+v"(eg_));
+    auto grow = [&](int rr) { return eg_ + PFML_F64_CROW(0, rr); };
+    int kb = kb0;
+    for (; kb < kend - 4 * S; kb += 4 * S) {
+      fstep(s0, kb + S, rsD, kb + 2 * S, nothing);
+      fstep(s1, kb + 2 * S, rsD, kb + 3 * S, nothing);
+      fstep(s2, kb + 3 * S, rsD, kb + 4 * S, nothing);
+      fstep(s3, kb + 4 * S, rsD, kb + 5 * S, nothing);
+      if (kb == kb0) {
+#pragma unroll
+        for (int q = 0; q < NTILE; ++q) acc[q] *= 0.5;
+      }
+    }
+    // The month's last four steps.  Every row is in range here, so the epilogue's loads are
+    // unconditional: r_i and D[i][n] (this month's own, from HBM) go out here, two steps
+    // before the month's last wait for beta, and beta_l[i], beta_l[n] in one batch after
+    // the last step (under `if (gi < n && l < L)` each of the 28 products waited for its own
+    // loads: 28 memory round trips in a row, more than the whole K loop of a 4-step tile).
+    double er[4], td[4];
+    fstep(s0, kb + S, rsD, kb + 2 * S, [&] {
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        er[rr] = rm[grow(rr)];
+        td[rr] = __builtin_bit_cast(
+            double, __builtin_amdgcn_raw_buffer_load_b64(rsD, grow(rr) * (int)ldD * 8, tn, 0));
+      }
+    });
+    fstep(s1, kb + 2 * S, rsD, kb + 3 * S, nothing);
+    fstep(s2, kb + 3 * S, rsN, nk0, nothing);
+    fstep(s3, kb0, rsN, nk1, nothing);
+    if (kb == kb0) {
+#pragma unroll
+      for (int q = 0; q < NTILE; ++q) acc[q] *= 0.5;
+    }
+    // Tail column and sums.  Columns l >= L compute on row L - 1's beta; nobody reads them.
+    // Two batches (4 + 3 column tiles): with the next month's first D fragments live, all
+    // 35 beta operands at once do not fit beside the accumulators in 168 VGPRs.
+    auto sums = [&](auto q0_c, auto q1_c) {
+      constexpr int q0 = decltype(q0_c)::value, q1 = decltype(q1_c)::value;
+      double eb[q1 - q0][4], tb[q1 - q0];
+#pragma unroll
+      for (int q = q0; q < q1; ++q) {
+        const int lo = min(q * 16 + er_, L - 1) * (int)ldB * 8;
+        tb[q - q0] =
+            __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rsB, lo, tn, 0));
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr)
+          eb[q - q0][rr] = __builtin_bit_cast(
+              double, __builtin_amdgcn_raw_buffer_load_b64(rsB, lo + grow(rr) * 8, 0, 0));
+      }
+#pragma unroll
+      for (int q = q0; q < q1; ++q) {
+        double s = 0.0;
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          const double u = tail ? fma(td[rr], tb[q - q0], acc[q][rr]) : acc[q][rr];
+          s += eb[q - q0][rr] * (er[rr] - u);          // u = U / 2
+        }
+        s += __shfl_xor(s, 16, 64);
+        s += __shfl_xor(s, 32, 64);
+        if (lane < 16) red[w][q * 16 + r] = s;
+      }
+    };
+    sums(std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{});
+    sums(std::integral_constant<int, 4>{}, std::integral_constant<int, NTILE>{});
+    __syncthreads();
+    if (t < L) {
+      double s = 0.0;
+#pragma unroll
+      for (int q = 0; q < NW; ++q) s += red[q][t];
+      partial[(int64_t)(jd.ptile0 + rt) * L + t] = s;
+    }
+    if (!more) break;
+    __syncthreads();                               // step 0 stages beta over the sums
+    jd = jn;
+    rsD = rsN;
   }
 }
 
@@ -365,9 +474,10 @@ __global__ __launch_bounds__(NT, 3) void quadform_direct_kernel(
 __global__ __launch_bounds__(NT, 3) void quadform_pipe_kernel(
     const double* __restrict__ D, int64_t ldD, const double* __restrict__ R,
     const double* __restrict__ Bt, int64_t ldB, const JobDesc* __restrict__ jobs,
-    const int* __restrict__ tile_job, int L, double* __restrict__ partial) {
+    const int* __restrict__ tile_job, const int* __restrict__ run_off, int L,
+    double* __restrict__ partial) {
   __shared__ __attribute__((aligned(16))) double Bs[2][NCOL * BK];
-  quad_direct_body<QD_PIPE>(Bs, D, ldD, R, Bt, ldB, jobs, tile_job, L, partial);
+  quad_pipe_body(Bs, D, ldD, R, Bt, ldB, jobs, tile_job, run_off, L, partial);
 }
 
 __global__ __launch_bounds__(NT, 3) void quadform_rest_kernel(
@@ -411,20 +521,24 @@ extern "C" int pfml_quadform_aligned(int n, int L, int64_t ldD, int64_t ldB) {
 
 // tile_job: one int32 per tile, job << 5 | row tile.  form: 3 = the direct-A form for every
 // tile; 4 = the pipelined form, every job of the launch aligned (pfml_quadform_aligned); 5 =
-// the pipelined form for the aligned jobs and the direct form's loop for the rest.  The
-// argument keeps the position and the values it had when 1 / 2 meant the retired LDS-staged
-// forms (months per tile), so a library built before their removal still loads under
-// PFML_HIP_LIB for an A/B against this one; 1 / 2 are refused here.
-extern "C" hipError_t pfml_quadform(const double* D, int64_t ldD, const double* R,
-                                    const double* Bt, int64_t ldB, const void* jobs, int njobs,
-                                    const int* tile_job, int ntiles, int form, int L,
-                                    double* partial, double* obj, hipStream_t st) {
+// the pipelined form for the aligned jobs and the direct form's loop for the rest.  run_off:
+// nullptr (every tile a workgroup of its own, nruns = ntiles), or nruns + 1 ascending offsets
+// into tile_job, run_off[0] = 0 and run_off[nruns] = ntiles: the pipelined kernel's
+// workgroup b walks tiles run_off[b] .. run_off[b + 1] - 1, which must be the same row tile
+// of jobs with the same n and beta block (forms 4 and 5 only; the direct form's loop takes
+// one tile per workgroup whatever the runs are).
+static hipError_t quadform_launch(const double* D, int64_t ldD, const double* R,
+                                  const double* Bt, int64_t ldB, const void* jobs, int njobs,
+                                  const int* tile_job, int ntiles, const int* run_off,
+                                  int nruns, int form, int L, double* partial, double* obj,
+                                  hipStream_t st) {
   if (njobs <= 0) return hipSuccess;
   if (L > NCOL || form < 3 || form > 5) return hipErrorInvalidValue;
+  if (run_off && (form < 4 || nruns <= 0 || nruns > ntiles)) return hipErrorInvalidValue;
   const JobDesc* jd = static_cast<const JobDesc*>(jobs);
   if (form >= 4) {
-    hipLaunchKernelGGL(quadform_pipe_kernel, dim3(ntiles), dim3(NT), 0, st, D, ldD, R, Bt, ldB,
-                       jd, tile_job, L, partial);
+    hipLaunchKernelGGL(quadform_pipe_kernel, dim3(run_off ? nruns : ntiles), dim3(NT), 0, st, D,
+                       ldD, R, Bt, ldB, jd, tile_job, run_off, L, partial);
     if (form == 5)
       hipLaunchKernelGGL(quadform_rest_kernel, dim3(ntiles), dim3(NT), 0, st, D, ldD, R, Bt,
                          ldB, jd, tile_job, L, partial);
@@ -434,4 +548,26 @@ extern "C" hipError_t pfml_quadform(const double* D, int64_t ldD, const double* 
   hipLaunchKernelGGL(quadform_reduce_kernel, dim3(njobs), dim3(128), 0, st, partial, jd, njobs, L,
                      D, ldD, R, Bt, ldB, obj);
   return hipGetLastError();
+}
+
+// One tile per workgroup.  The `form` argument keeps the position and the values it had when
+// 1 / 2 meant the retired LDS-staged forms (months per tile), so a library built before their
+// removal still loads under PFML_HIP_LIB for an A/B against this one; 1 / 2 are refused here.
+extern "C" hipError_t pfml_quadform(const double* D, int64_t ldD, const double* R,
+                                    const double* Bt, int64_t ldB, const void* jobs, int njobs,
+                                    const int* tile_job, int ntiles, int form, int L,
+                                    double* partial, double* obj, hipStream_t st) {
+  return quadform_launch(D, ldD, R, Bt, ldB, jobs, njobs, tile_job, ntiles, nullptr, ntiles,
+                         form, L, partial, obj, st);
+}
+
+// The pipelined form over runs of tiles (form 4 or 5, run_off as above).
+extern "C" hipError_t pfml_quadform_runs(const double* D, int64_t ldD, const double* R,
+                                         const double* Bt, int64_t ldB, const void* jobs,
+                                         int njobs, const int* tile_job, int ntiles,
+                                         const int* run_off, int nruns, int form, int L,
+                                         double* partial, double* obj, hipStream_t st) {
+  if (!run_off) return hipErrorInvalidValue;
+  return quadform_launch(D, ldD, R, Bt, ldB, jobs, njobs, tile_job, ntiles, run_off, nruns,
+                         form, L, partial, obj, st);
 }

@@ -34,6 +34,9 @@ def _declare_hip(lib):
     lib.pfml_ridge_band_nmax.restype = I
     lib.pfml_quadform.argtypes = [P, L, P, P, L, P, I, P, I, I, I, P, P, P]
     lib.pfml_quadform.restype = I
+    if hasattr(lib, "pfml_quadform_runs"):       # absent from a PFML_HIP_LIB build that predates it
+        lib.pfml_quadform_runs.argtypes = [P, L, P, P, L, P, I, P, I, P, I, I, I, P, P, P]
+        lib.pfml_quadform_runs.restype = I
     lib.pfml_quadform_job_desc_size.restype = I
     lib.pfml_quadform_rows_per_tile.restype = I
     lib.pfml_quadform_row_tiles.argtypes = [I]

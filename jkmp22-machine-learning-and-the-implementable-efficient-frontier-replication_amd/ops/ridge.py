@@ -350,6 +350,11 @@ COOP_KMAX = 16          # workgroups per cell of the cooperative band reduction 
 COOP_SYNC_WORDS = 32    # csrc/ridge_band.h COOP_SYNC (pfml_coop_sync_words): int32 sync words per cell
 COOP_BIG_SHARE = 0.42   # share of the CUs the largest cells' cooperative launch gets (coop_k)
 QUAD_DIRECT, QUAD_PIPE, QUAD_PIPE_REST = 3, 4, 5     # csrc/quadform.hip pfml_quadform's `form`
+# K steps the longest run of a utilities launch may take: the months of every (cell, row
+# tile) are cut into runs of as many months as keep the longest tile's run within this
+# (``quad_plan``; profiles/r16_experiments.md)
+QUAD_RUN_STEPS = 192
+QUAD_SLOTS_PER_CU = 3   # utilities workgroups resident per CU (csrc/quadform.hip launch bounds)
 
 
 @dataclass(frozen=True)
@@ -782,9 +787,10 @@ def _utilities_plan(P: int, L: int, dev, cell_src, cell_n, cell_scale, job_cell,
         rp = ridge_plan(P, L, cell_src[cells], cell_n[cells], cell_scale[cells], num_cus(dev), sw)
         # ridge_plan orders cells big-first and numbers outputs 0..: map to global rows
         rp["desc"]["out"] = cells[rp["desc"]["out"] // (L * P)].astype(np.int64) * L * P
-        qp = quad_plan(P, L, P, job_cell[jobs], job_month[jobs], job_n[jobs], job_out=jobs, sw=sw)
+        qp = quad_plan(P, L, P, job_cell[jobs], job_month[jobs], job_n[jobs], job_out=jobs, sw=sw,
+                       run_steps=QUAD_RUN_STEPS, slots=QUAD_SLOTS_PER_CU * num_cus(dev))
         groups.append((cells, jobs, rp, qp))
-        arrays += [rp["desc"], qp["desc"], qp["tile_job"], rp["wgmap"]]
+        arrays += [rp["desc"], qp["desc"], quad_tables(qp), rp["wgmap"]]
     dv = upload(arrays, dev)                     # all descriptors, one async copy
     plan = {"groups": groups, "dv": dv}
     if len(_UTIL_PLANS) > 64:
@@ -881,10 +887,25 @@ def ridge_utilities(SD: torch.Tensor, Sr: torch.Tensor, cell_src, cell_n, cell_s
 
 
 def quad_plan(P: int, L: int, Pb: int, job_cell, job_month, job_n, job_out=None,
-              sw: Switches | None = None) -> dict:
+              sw: Switches | None = None, run_steps: int | None = None,
+              run_months: int | None = None, slots: int | None = None) -> dict:
     """Host-side descriptors of one utilities launch: JOB_DTYPE per job and ``tile_job``, one
     int32 ``job << 5 | row tile`` per 64-row tile in launch order.  ``job_out``: row of each
-    job in the obj array the launch writes (default: 0..nj-1)."""
+    job in the obj array the launch writes (default: 0..nj-1).
+
+    ``run_steps`` / ``run_months`` (neither: one tile per workgroup, ``run_off`` None) select
+    the run form: the months of every (cell, row tile) are cut into runs that one workgroup
+    walks back to back (csrc/quadform.hip quad_pipe_body), and ``run_off`` holds the runs'
+    offsets into ``tile_job``.  ``run_steps``: as many months per run as keep a run of the
+    launch's longest tile within that many K steps and within the launch's K steps per
+    workgroup slot (``slots``, default 3 per CU of a 256-CU chip: small launches keep fine
+    work units), the same number for every tile of the launch and the months spread evenly
+    over a group's runs - so a run is as much shorter as its tile is, and the launch, longest
+    first, still ends on short work units (runs levelled to one length in K steps left the
+    chip's tail idle and measured slower, profiles/r16_experiments.md).  ``run_months``:
+    exactly that many months per run (the last run of a group takes what is left), whatever
+    the launch's size.  Tiles that are not aligned stay runs of one.  Results do not depend
+    on the runs (bitwise)."""
     sw = sw or switches()
     lib = nat.hip_lib()
     if lib.pfml_quadform_job_desc_size() != JOB_DTYPE.itemsize:
@@ -915,27 +936,98 @@ def quad_plan(P: int, L: int, Pb: int, job_cell, job_month, job_n, job_out=None,
     # entry = job << 5 | rt (the kernel writes partial slot ptile0 + rt of the job)
     jt = np.repeat(by_cell, jnt)
     rt = np.arange(len(jt), dtype=np.int64) - np.repeat(np.cumsum(jnt) - jnt, jnt)
-    order = np.argsort(rt, kind="stable")
-    jt, rt = jt[order], rt[order]
-    if len(jt) and sw.quad_xcd:
-        jt, rt = _xcd_affine(jt, rt, jc[jt])
+    is_aligned = {n: bool(lib.pfml_quadform_aligned(n, L, P, Pb)) for n in tiles_of}
+    run_off = None
+    if len(jt) and (run_steps or run_months):
+        jt, rt, run_off = _quad_runs(jt, rt, jc, job_n, is_aligned, run_steps,
+                                     run_months, slots or QUAD_SLOTS_PER_CU * 256,
+                                     sw.quad_xcd)
+    else:
+        order = np.argsort(rt, kind="stable")
+        jt, rt = jt[order], rt[order]
+        if len(jt) and sw.quad_xcd:
+            order = _xcd_order(jc[jt])
+            jt, rt = jt[order], rt[order]
     tile_job = ((jt << 5) | rt).astype(np.int32)
-    aligned = all(lib.pfml_quadform_aligned(n, L, P, Pb) for n in tiles_of)
-    return {"desc": desc, "tile_job": tile_job, "nj": nj, "ntiles": len(jt),
-            "nslots": int(ntile.sum()), "pipe": QUAD_PIPE if aligned else QUAD_PIPE_REST}
+    return {"desc": desc, "tile_job": tile_job, "run_off": run_off, "nj": nj,
+            "ntiles": len(jt), "nslots": int(ntile.sum()),
+            "pipe": QUAD_PIPE if all(is_aligned.values()) else QUAD_PIPE_REST}
+
+
+def quad_tile_steps(job_n, jt: np.ndarray, rt: np.ndarray) -> np.ndarray:
+    """K steps of 16 of each tile (job jt, row tile rt): a row tile walks the indices from its
+    own first row to the job's last (csrc/quadform.hip quad_main: a tail index n - 1 that is
+    a multiple of 16 is not walked)."""
+    n = np.asarray(job_n, np.int64)[jt]
+    nmain = np.where((n > 1) & ((n - 1) % 16 == 0), n - 1, n)
+    return -(-(nmain - 64 * rt) // 16)
+
+
+def _quad_runs(jt, rt, jc, job_n, is_aligned, run_steps, run_months, slots, xcd):
+    """Cut the tiles (jt, rt: cell-major, a cell's months in order, row tiles innermost) into
+    runs - one (cell, n, row tile) over consecutive months of that group - order the runs
+    longest first (per XCD queue when ``xcd``), and return the tiles in launch order with the
+    runs' offsets."""
+    steps = quad_tile_steps(job_n, jt, rt)
+    cap = int(steps.sum()) // max(1, slots)        # the launch's K steps per workgroup slot
+    # tiles by (cell, n, row tile), months in their order within
+    order = np.lexsort((np.arange(len(jt)), rt, np.asarray(job_n)[jt], jc[jt]))
+    jt, rt, steps = jt[order], rt[order], steps[order]
+    key = np.stack([jc[jt], np.asarray(job_n, np.int64)[jt], rt], axis=1)
+    new = np.concatenate([[True], (key[1:] != key[:-1]).any(axis=1)])
+    starts = np.nonzero(new)[0]
+    ends = np.concatenate([starts[1:], [len(jt)]])
+    # months per run by the step target: what keeps a run of the launch's longest tile within
+    # it and within the launch's steps per slot; every shorter tile gets as many months
+    alig = np.array([is_aligned[int(v)] for v in np.asarray(job_n)[jt]])
+    kmonths = max(1, min(int(run_steps or 0), cap) // int(steps[alig].max())) if alig.any() else 1
+    offs = []                                      # run boundaries within the sorted tiles
+    for a, b in zip(starts, ends):
+        nm, st = int(b - a), int(steps[a])
+        if not is_aligned[int(job_n[jt[a]])]:
+            k = 1
+        elif run_months:
+            k = int(run_months)
+        else:
+            k = kmonths
+        if run_months or k >= nm or k == 1:
+            cuts = np.arange(a, b, max(1, min(k, nm)))
+        else:                                      # level the group's runs
+            nr = -(-nm // k)
+            cuts = a + (np.arange(nr) * nm) // nr
+        offs.append(cuts)
+    r0 = np.concatenate(offs)
+    r1 = np.concatenate([r0[1:], [len(jt)]])
+    rlen = steps[r0] * (r1 - r0)
+    rorder = np.argsort(-rlen, kind="stable")       # longest first
+    if xcd:
+        rorder = rorder[_xcd_order(jc[jt[r0[rorder]]])]
+    r0, r1 = r0[rorder], r1[rorder]
+    tiles = np.concatenate([np.arange(a, b) for a, b in zip(r0, r1)])
+    run_off = np.concatenate([[0], np.cumsum(r1 - r0)]).astype(np.int32)
+    return jt[tiles], rt[tiles], run_off
+
+
+def quad_tables(plan: dict) -> np.ndarray:
+    """The int32 table a utilities launch reads on the device: ``tile_job``, followed by the
+    runs' offsets when the plan has runs (``quad_launch`` tells them apart by the plan)."""
+    if plan["run_off"] is None:
+        return plan["tile_job"]
+    return np.concatenate([plan["tile_job"], plan["run_off"]]).astype(np.int32)
 
 
 NXCD = 8   # MI355X: workgroup b of a launch is dispatched to XCD b mod 8
 
 
-def _xcd_affine(jobs_t: np.ndarray, rt: np.ndarray, cell: np.ndarray):
-    """Reorder a utilities launch's tiles (kept in their longest-first order per XCD) so that
-    every tile of one cell runs on XCD ``cell mod 8``: slot s of the launch goes to XCD s mod 8
-    and takes the next tile of that XCD's queue (cells numbered densely within the launch).  A cell's beta block (L x n, ~0.4 MB at
-    n = 513) is then read by its 12 months x row tiles through ONE L2 instead of all eight -
-    in launch order every XCD saw every cell, and the L2s kept re-fetching beta from HBM.
-    Queues that run dry hand their slots to the longest remaining one (the tail loses the
-    affinity, not the order)."""
+def _xcd_order(cell: np.ndarray) -> np.ndarray:
+    """Launch order of a utilities launch's work units (tiles, or runs of tiles; given in
+    their longest-first order, which is kept per XCD) so that every unit of one cell runs on
+    XCD ``cell mod 8``: slot s of the launch goes to XCD s mod 8 and takes the next unit of
+    that XCD's queue (cells numbered densely within the launch).  A cell's beta block (L x n,
+    ~0.4 MB at n = 513) is then read by its 12 months x row tiles through ONE L2 instead of
+    all eight - in launch order every XCD saw every cell, and the L2s kept re-fetching beta
+    from HBM.  Queues that run dry hand their slots to the longest remaining one (the tail
+    loses the affinity, not the order)."""
     _, x = np.unique(np.asarray(cell, np.int64), return_inverse=True)   # dense cell ranks
     x = x.reshape(-1) % NXCD
     queues = [list(np.nonzero(x == k)[0]) for k in range(NXCD)]
@@ -947,6 +1039,12 @@ def _xcd_affine(jobs_t: np.ndarray, rt: np.ndarray, cell: np.ndarray):
             k = int(np.argmax([len(q) - h for q, h in zip(queues, heads)]))
         order[s] = queues[k][heads[k]]
         heads[k] += 1
+    return order
+
+
+def _xcd_affine(jobs_t: np.ndarray, rt: np.ndarray, cell: np.ndarray):
+    """``_xcd_order`` applied to a launch's single tiles."""
+    order = _xcd_order(cell)
     return jobs_t[order], rt[order]
 
 
@@ -954,21 +1052,32 @@ def quad_launch(plan: dict, d_desc: torch.Tensor, d_tj: torch.Tensor, D: torch.T
                 R: torch.Tensor, beta: torch.Tensor, obj: torch.Tensor,
                 sw: Switches | None = None) -> None:
     """Queue one utilities launch (csrc/quadform.hip) of a ``quad_plan`` made for these P, L
-    and beta row stride.  Default: the pipelined loop for the aligned jobs - QUAD_PIPE when
-    every job is aligned, as in production, else QUAD_PIPE_REST, which adds a launch of the
-    direct form's loop for the rest.  ``sw.quad_direct``: the direct form for every tile."""
+    and beta row stride; ``d_tj`` is the device copy of ``quad_tables(plan)``.  Default: the
+    pipelined loop for the aligned jobs - QUAD_PIPE when every job is aligned, as in
+    production, else QUAD_PIPE_REST, which adds a launch of the direct form's loop for the
+    rest - over the plan's runs when it has any.  ``sw.quad_direct``: the direct form for
+    every tile, one per workgroup (the runs are not used)."""
     sw = sw or switches()
     if plan["nj"] == 0:
         return
     P = D.shape[-1]
     L, Pb = beta.shape[1], beta.shape[2]
     partial = torch.empty((plan["nslots"], L), dtype=torch.float64, device=D.device)
-    form = QUAD_DIRECT if sw.quad_direct else plan["pipe"]
-    nat.check(nat.hip_lib().pfml_quadform(D.data_ptr(), P, R.data_ptr(), beta.data_ptr(), Pb,
-                                          d_desc.data_ptr(), plan["nj"], d_tj.data_ptr(),
-                                          plan["ntiles"], form, L,
-                                          partial.data_ptr(), obj.data_ptr(),
-                                          nat.stream_of(D)), "pfml_quadform")
+    lib = nat.hip_lib()
+    args = (D.data_ptr(), P, R.data_ptr(), beta.data_ptr(), Pb, d_desc.data_ptr(), plan["nj"],
+            d_tj.data_ptr(), plan["ntiles"])
+    tail = (L, partial.data_ptr(), obj.data_ptr(), nat.stream_of(D))
+    run_off = plan.get("run_off")
+    if run_off is None or sw.quad_direct:
+        form = QUAD_DIRECT if sw.quad_direct else plan["pipe"]
+        nat.check(lib.pfml_quadform(*args, form, *tail), "pfml_quadform")
+        return
+    if d_tj.numel() * d_tj.element_size() != 4 * (plan["ntiles"] + len(run_off)):
+        raise ValueError("quad_launch: the plan has runs, so d_tj must be the upload of "
+                         "quad_tables(plan) (tile_job followed by run_off)")
+    nat.check(lib.pfml_quadform_runs(*args, d_tj.data_ptr() + 4 * plan["ntiles"],
+                                     len(run_off) - 1, plan["pipe"], *tail),
+              "pfml_quadform")       # one name for the utilities launch, whichever entry
 
 
 def quadform_utilities(D: torch.Tensor, R: torch.Tensor, beta: torch.Tensor,
@@ -983,8 +1092,9 @@ def quadform_utilities(D: torch.Tensor, R: torch.Tensor, beta: torch.Tensor,
         return obj
     if nat.is_device(D):
         sw = switches()
-        plan = quad_plan(P, L, Pb, job_cell, job_month, job_n, sw=sw)
-        d_desc, d_tj = upload([plan["desc"], plan["tile_job"]], D.device)
+        plan = quad_plan(P, L, Pb, job_cell, job_month, job_n, sw=sw, run_steps=QUAD_RUN_STEPS,
+                         slots=QUAD_SLOTS_PER_CU * num_cus(D.device))
+        d_desc, d_tj = upload([plan["desc"], quad_tables(plan)], D.device)
         quad_launch(plan, d_desc, d_tj, D.contiguous(), R.contiguous(), beta.contiguous(), obj, sw)
         return obj
     for j in range(nj):
