@@ -1,82 +1,29 @@
-// Segmented sums over the month axis.
+// Expanding-window sums of the grid search over the month axis.
 //
 // The reference keeps running sums of r_tilde and denom, adding each hyper-parameter year's
-// 12 new months (PFML_Search_Coef.py:68-121).  The engine instead sums each window segment
-// (burn-in block, then one block per hp year) in one bandwidth-bound pass over the resident
-// [T, E] stack and prefix-sums the per-segment totals (53 x E, negligible).  For the 513 x 513
-// denom stack this reads 2.1 MB per month exactly once; rows of even length that are 16-byte
-// aligned take the double2 (16 B per lane) path.
-//
-// The hp-year windows of the grid search follow one canonical chunked association (below).  A
-// rank of a multi-rank run forms them with two kernels around an all-gather of chunk totals
-// (pfml_wsum_chunk_totals, pfml_wsum_chunk_prefix, pfml_wvec_chunk); a one-rank run takes
-// pfml_wsum_onepass, ONE launch that reads every month's upper triangle once and writes the
-// mirrored windows once, bitwise the same.
+// 12 new months (PFML_Search_Coef.py:68-121).  The engine sums the resident [G, T, P, P] /
+// [G, T, P] month stacks per window segment (burn-in pieces, then one block per hp year) and
+// folds the segments in ONE canonical chunked association (below), so every world size adds
+// the same numbers in the same order.  A rank of a multi-rank run forms its windows with two
+// kernels around an all-gather of chunk totals (pfml_wsum_chunk_totals, pfml_wsum_chunk_prefix,
+// pfml_wvec_chunk); a one-rank run takes pfml_wsum_onepass, ONE launch that reads every
+// month's upper triangle once and writes the mirrored windows once, bitwise the same.
 #include "common.h"
 
 namespace {
 
-template <int VEC>
-__global__ __launch_bounds__(256) void segsum_kernel(const double* __restrict__ X, int64_t E,
-                                                     const int* __restrict__ seg_start,
-                                                     const int* __restrict__ seg_stop,
-                                                     double* __restrict__ out) {
-  const int s = blockIdx.y;
-  const int64_t e0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
-  if (e0 >= E) return;
-  const int a = seg_start[s], b = seg_stop[s];
-  if (VEC == 2) {
-    double2 acc = {0.0, 0.0};
-    for (int tm = a; tm < b; ++tm) {
-      const double2 x = *reinterpret_cast<const double2*>(X + (int64_t)tm * E + e0);
-      acc.x += x.x;
-      acc.y += x.y;
-    }
-    *reinterpret_cast<double2*>(out + (int64_t)s * E + e0) = acc;
-  } else {
-    double acc = 0.0;
-    for (int tm = a; tm < b; ++tm) acc += X[(int64_t)tm * E + e0];
-    out[(int64_t)s * E + e0] = acc;
-  }
-}
-
-}  // namespace
-
-// X: [T, E] row-major, out: [S, E]; segment s sums rows [seg_start[s], seg_stop[s]).
-extern "C" hipError_t pfml_segsum(const double* X, int64_t E, const int* seg_start,
-                                  const int* seg_stop, int nseg, double* out, hipStream_t st) {
-  if (nseg <= 0 || E <= 0) return hipSuccess;
-  const bool vec = (E % 2 == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0) &&
-                   ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-  if (vec) {
-    dim3 grid((unsigned)((E / 2 + 255) / 256), nseg);
-    hipLaunchKernelGGL(segsum_kernel<2>, grid, dim3(256), 0, st, X, E, seg_start, seg_stop, out);
-  } else {
-    dim3 grid((unsigned)((E + 255) / 256), nseg);
-    hipLaunchKernelGGL(segsum_kernel<1>, grid, dim3(256), 0, st, X, E, seg_start, seg_stop, out);
-  }
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------
-// Expanding-window sums of symmetric month matrices (K14, fused prefix):
-//   out[g, s] = sum over segments s' <= s of sum_{t in [start_s', stop_s')} X[g, t]
-// X: [G, T, P, P] (each X[g, t] symmetric), out: [G, S, P, P] (full, symmetric).
-// Pass 1 sums every (row, segment) over the UPPER triangle only (half the bytes of a dense
-// pass, one workgroup per (row, segment, g) for full-chip parallelism) into out; pass 2 runs
-// the prefix over segments in place and mirrors (i, j) to (j, i).  The dense segment sums +
-// torch cumsum it replaces read 2x and wrote 3x as much.
-namespace {
-
 // Segment s's sums live in out[g][s - skip] for s >= skip and in scratch[g][s] for the
-// leading `skip` segments (e.g. the burn-in block, needed only as a prefix): the output is
-// the contiguous [G][nseg - skip] stack the ridge grid consumes, with no slicing copy.
+// leading `skip` segments (the burn-in pieces, needed only as a prefix): the output is the
+// contiguous [G][nseg - skip] stack the ridge grid consumes, with no slicing copy.
 __device__ __forceinline__ double* seg_slot(double* out, double* scratch, int g, int s, int nseg,
                                             int skip, int64_t PP) {
   return s < skip ? scratch + ((int64_t)g * skip + s) * PP
                   : out + ((int64_t)g * (nseg - skip) + (s - skip)) * PP;
 }
 
+// Segment sums of the symmetric month matrices X [G, T, P, P] into their seg_slot: the UPPER
+// triangle only (half the bytes of a dense pass), one workgroup per (row, segment, g) for
+// full-chip parallelism.  The chunk kernels below fold and mirror them.
 __global__ __launch_bounds__(256) void wsum_upper_kernel(const double* __restrict__ X, int P,
                                                          int T, const int* __restrict__ seg_start,
                                                          const int* __restrict__ seg_stop,
@@ -101,94 +48,18 @@ __global__ __launch_bounds__(256) void wsum_upper_kernel(const double* __restric
   }
 }
 
-// pass 2 on 32 x 32 tiles (I <= J) of the upper triangle: running sum over segments in
-// registers, tile (I, J) and its transpose (J, I) both written row-contiguous via LDS.  The
-// next segment's tile is loaded while the current one is written (loads clamped into the
-// matrix, masked on use).
-__global__ __launch_bounds__(256) void wsum_prefix_mirror_kernel(int P, int nseg, int skip,
-                                                                 double* __restrict__ out,
-                                                                 double* __restrict__ scratch) {
-  __shared__ double Ts[32][33];
-  const int g = blockIdx.y;
-  int tile = blockIdx.x;
-  const int nt = (P + 31) / 32;
-  int I = 0;                                    // upper tiles enumerated row by row
-  while (tile >= nt - I) { tile -= nt - I; ++I; }
-  const int J = I + tile;
-  const int64_t PP = (int64_t)P * P;
-  const int t = threadIdx.x, c = t & 31, r0 = t >> 5;
-  double acc[4] = {0.0, 0.0, 0.0, 0.0}, nx[4];
-  auto fetch = [&](int s) {
-    const double* o = seg_slot(out, scratch, g, s, nseg, skip, PP);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int i = min(I * 32 + r0 + 8 * q, P - 1), j = min(J * 32 + c, P - 1);
-      nx[q] = o[(int64_t)i * P + j];
-    }
-  };
-  fetch(0);
-  for (int s = 0; s < nseg; ++s) {
-    double cur[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) cur[q] = nx[q];
-    if (s + 1 < nseg) fetch(s + 1);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int r = r0 + 8 * q, i = I * 32 + r, j = J * 32 + c;
-      const bool valid = i < P && j < P && (I != J || c >= r);
-      acc[q] += valid ? cur[q] : 0.0;
-      Ts[r][c] = acc[q];
-    }
-    __syncthreads();
-    if (s >= skip) {
-      double* o = seg_slot(out, scratch, g, s, nseg, skip, PP);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int r = r0 + 8 * q;
-        const int i = I * 32 + r, j = J * 32 + c;
-        if (i < P && j < P) o[(int64_t)i * P + j] = (I != J || c >= r) ? Ts[r][c] : Ts[c][r];
-        const int i2 = J * 32 + r, j2 = I * 32 + c;     // transposed tile
-        if (I != J && i2 < P && j2 < P) o[(int64_t)i2 * P + j2] = Ts[c][r];
-      }
-    }
-    __syncthreads();
-  }
-}
-
-}  // namespace
-
-extern "C" hipError_t pfml_window_prefix_sym(const double* X, int P, int T, int G,
-                                             const int* seg_start, const int* seg_stop, int nseg,
-                                             int skip, double* out, double* scratch,
-                                             hipStream_t st) {
-  if (nseg <= 0 || P <= 0 || G <= 0) return hipSuccess;
-  if (skip < 0 || skip > nseg || (skip > 0 && scratch == nullptr)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(wsum_upper_kernel, dim3(P, nseg, G), dim3(256), 0, st, X, P, T, seg_start,
-                     seg_stop, nseg, skip, out, scratch);
-  const int nt = (P + 31) / 32;
-  hipLaunchKernelGGL(wsum_prefix_mirror_kernel, dim3(nt * (nt + 1) / 2, G), dim3(256), 0, st, P,
-                     nseg, skip, out, scratch);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------
-// Expanding-window sums of the month VECTORS (r_tilde) in one launch:
-//   out[g, s - skip, c] = sum over segments s' <= s of sum_{t in [start_s', stop_s')} X[g, t, c]
-// X: [G, T, E], out: [G, nseg - skip, E].  Workgroup (64 columns, g): its 16 row groups sum
-// the segments (eight months in flight per lane) into LDS, then one row group runs the
-// prefix over the segments in segment order.  Replaces segment sums + a transposing copy,
-// a scan and two copies (~55 us of small launches ahead of the ridge grid).
-namespace {
+// Segment sums of the month VECTORS (r_tilde): a workgroup of RG row groups x COLS columns
+// holds every segment's sums of its columns in LDS (at most WV_SEG segments).  Row group ry
+// fills part[s][lc] for s = ry, ry + RG, ...: eight independent chains (eight months in
+// flight per lane, the months past the segment's end masked to +0.0), folded pairwise.  src
+// points at the thread's column of month 0 and E is the month pitch.  The ONE copy of this
+// loop: the two-kernel path and the one-pass kernel are bitwise alike because both call it.
 constexpr int WV_COLS = 64, WV_SEG = 128, WV_T = 1024, WV_RG = WV_T / WV_COLS;
-__global__ __launch_bounds__(WV_T) void window_prefix_vec_kernel(
-    const double* __restrict__ X, int64_t E, int T, const int* __restrict__ seg_start,
-    const int* __restrict__ seg_stop, int nseg, int skip, double* __restrict__ out) {
-  __shared__ double part[WV_SEG][WV_COLS];
-  const int lc = threadIdx.x % WV_COLS, ry = threadIdx.x / WV_COLS;
-  const int g = blockIdx.y, c = blockIdx.x * WV_COLS + lc;
-  const bool cv = c < E;
-  const double* src = X + (int64_t)g * T * E + (cv ? c : 0);
-  for (int s = ry; s < nseg; s += WV_RG) {
+template <int COLS, int RG>
+__device__ __forceinline__ void wvec_segsums(const double* src, int64_t E, const int* seg_start,
+                                             const int* seg_stop, int nseg, int ry, int lc,
+                                             double (*part)[COLS]) {
+  for (int s = ry; s < nseg; s += RG) {
     const int a = seg_start[s], b = seg_stop[s];
     double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int tm = a; tm < b; tm += 8) {          // eight months in flight
@@ -200,29 +71,9 @@ __global__ __launch_bounds__(WV_T) void window_prefix_vec_kernel(
     }
     part[s][lc] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
   }
-  __syncthreads();
-  if (ry == 0 && cv) {
-    double run = 0.0;
-    double* o = out + (int64_t)g * (nseg - skip) * E + c;
-    for (int s = 0; s < nseg; ++s) {
-      run += part[s][lc];
-      if (s >= skip) o[(int64_t)(s - skip) * E] = run;
-    }
-  }
 }
+
 }  // namespace
-
-extern "C" int pfml_window_prefix_vec_max_segments() { return WV_SEG; }
-
-extern "C" hipError_t pfml_window_prefix_vec(const double* X, int64_t E, int T, int G,
-                                             const int* seg_start, const int* seg_stop, int nseg,
-                                             int skip, double* out, hipStream_t st) {
-  if (nseg <= 0 || E <= 0 || G <= 0 || nseg - skip <= 0) return hipSuccess;
-  if (nseg > WV_SEG || skip < 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(window_prefix_vec_kernel, dim3((unsigned)((E + WV_COLS - 1) / WV_COLS), G),
-                     dim3(WV_T), 0, st, X, E, T, seg_start, seg_stop, nseg, skip, out);
-  return hipGetLastError();
-}
 
 // ---------------------------------------------------------------------------------------
 // Canonical chunked expanding-window sums (bitwise the same on every world size).
@@ -384,7 +235,8 @@ __global__ __launch_bounds__(256) void wsum_chunk_prefix_kernel(
 }
 
 // vectors (r_tilde): mode 0 = chunk totals into tot[g][slot[lc]][E], mode 1 = windows into
-// out[g][s - skip][E].  Segment sums as window_prefix_vec_kernel (eight months in flight).
+// out[g][s - skip][E].  Workgroup (64 columns, g): its 16 row groups sum the segments into LDS
+// (wvec_segsums), then one row group runs the folds in canonical order.
 __global__ __launch_bounds__(WV_T) void wvec_chunk_kernel(
     const double* __restrict__ X, int64_t E, int T, const int* __restrict__ seg_start,
     const int* __restrict__ seg_stop, int nseg, int skip, int mode, int nlc,
@@ -397,18 +249,7 @@ __global__ __launch_bounds__(WV_T) void wvec_chunk_kernel(
   const int g = blockIdx.y, col = blockIdx.x * WV_COLS + lc;
   const bool cv = col < E;
   const double* src = X + (int64_t)g * T * E + (cv ? col : 0);
-  for (int s = ry; s < nseg; s += WV_RG) {
-    const int a = seg_start[s], b = seg_stop[s];
-    double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int tm = a; tm < b; tm += 8) {
-      double x[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) x[u] = (tm + u < b) ? src[(int64_t)(tm + u) * E] : 0.0;
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc[u] += x[u];
-    }
-    part[s][lc] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-  }
+  wvec_segsums<WV_COLS, WV_RG>(src, E, seg_start, seg_stop, nseg, ry, lc, part);
   __syncthreads();
   if (ry != 0 || !cv) return;
   double* tg = tot + (int64_t)g * E + col;     // slot k at tg + k * tstride
@@ -673,25 +514,14 @@ __global__ __launch_bounds__(OP_T) void wsum_onepass_kernel(
                      clast, SD, smem);
     return;
   }
-  // the vectors: segment sums as wvec_chunk_kernel (OP_VRG row groups, eight months in
-  // flight), then its mode 0 and mode 1 folds with the totals kept in a register
+  // the vectors: wvec_chunk_kernel's segment sums (OP_VRG row groups of OP_VC columns), then
+  // its mode 0 and mode 1 folds with the totals kept in a register
   double (*part)[OP_VC] = reinterpret_cast<double (*)[OP_VC]>(smem);
   const int lc = threadIdx.x % OP_VC, ry = threadIdx.x / OP_VC;
   const int col = blockIdx.x * OP_VC + lc;
   const bool cv = col < P;
   const double* src = R + (int64_t)g * T * P + (cv ? col : 0);
-  for (int s = ry; s < nseg; s += OP_VRG) {
-    const int a = seg_start[s], b = seg_stop[s];
-    double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int tm = a; tm < b; tm += 8) {
-      double x[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) x[u] = (tm + u < b) ? src[(int64_t)(tm + u) * P] : 0.0;
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc[u] += x[u];
-    }
-    part[s][lc] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-  }
+  wvec_segsums<OP_VC, OP_VRG>(src, P, seg_start, seg_stop, nseg, ry, lc, part);
   __syncthreads();
   if (ry != 0 || !cv) return;
   double pc = 0.0;

@@ -4,8 +4,9 @@ Replaces PFML_Search_Coef.py (expanding running sums + 101 ``np.linalg.solve`` p
 (g, year, p), :60-143) and PFML_hp_reals.py (one quadratic form per (g, year, p, lambda,
 month) from Python, :62-130) with one batched device pipeline:
 
-1. window sums   - one segmented-sum pass over the resident [G, T, P, P] / [G, T, P] stacks
-                   (burn-in block + one block per hp year), prefix over blocks (K14);
+1. window sums   - expanding sums of the resident [G, T, P, P] / [G, T, P] stacks per hp year
+                   in the canonical chunk order below: one launch at world size one, two
+                   kernels around an all-gather of chunk totals otherwise (K14, ops/wsum.py);
 2. ridge grid    - band reduction (bandwidth 16) per (g, year, p) cell, a banded Cholesky
                    per lambda and a blocked-WY back-transform (K15, csrc/ridge_band.hip);
 3. utilities     - fused D_t B GEMM + dot epilogue per (cell, validation month) (K16);
@@ -35,7 +36,9 @@ import torch
 
 from ..config import Config
 from ..ops import _native as nat
-from ..ops.ridge import _HostClock, ridge_utilities, window_prefix_sym, window_prefix_vec
+from ..ops.ridge import _HostClock, ridge_utilities
+from ..ops.wsum import (WindowPlan, chunk_totals, chunk_windows, window_plan,
+                        window_sums_onepass)
 from ..parallel import collectives as coll
 from ..parallel.dist import env as dist_env
 from ..utils.dates import mi_from_ym, month_end
@@ -162,6 +165,53 @@ def _water_fill(total: int, base: np.ndarray) -> np.ndarray:
 
 def chunk_owner(c: int, C: int, world: int) -> int:
     return c * world // C
+
+
+def rank_window_plan(plan: "SearchPlan", lay: WinLayout, world: int, rank: int,
+                     rows: np.ndarray, T: int, dev) -> WindowPlan:
+    """``rank``'s share of the layout as the window-sum kernels take it (``rows``: the global
+    month rows it holds, sorted; T of them): its segments in month order - the owned burn-in
+    pieces (prefix only), then the blocks of the owned years - its chunks over them, and the
+    canonical slots of the gathered chunk totals: rank blocks in rank order, each rank's burn
+    pieces, then its year chunks, ascending."""
+    C = lay.C
+    own = [c for c in range(C) if chunk_owner(c, C, world) == rank]
+    seg = []                                     # (first, last + 1) local month row
+    cs, ce = [], []
+    for k in own:
+        cs.append(len(seg))
+        seg.append(_local_rows(rows, rank, *lay.burn[k], "burn-in piece"))
+        ce.append(len(seg))
+    skip = len(seg)
+    ys, ye = [0] * C, [0] * C
+    for c in own:
+        ys[c] = len(seg)
+        seg += [_local_rows(rows, rank, int(plan.seg_start[y]), int(plan.seg_stop[y]),
+                            "window blocks") for y in lay.ychunks[c]]
+        ye[c] = len(seg)
+        cs.append(ys[c])
+        ce.append(ye[c])
+    counts, sb, sy, off = [], [0] * C, [0] * C, 0
+    for r in range(world):
+        ro = [c for c in range(C) if chunk_owner(c, C, world) == r]
+        for i, k in enumerate(ro):
+            sb[k] = off + i
+            sy[k] = off + len(ro) + i
+        counts.append(2 * len(ro))
+        off += 2 * len(ro)
+    clast = max(own) if len(seg) > skip else -1
+    return window_plan(T=T, skip=skip, C=C, clast=clast, counts=counts,
+                       st=[a for a, _ in seg], sp=[b for _, b in seg], cs=cs, ce=ce,
+                       slot=np.arange(len(cs)),          # local totals: local order
+                       sb=sb, sy=sy, ys=ys, ye=ye, dev=dev, who=f"rank {rank}")
+
+
+def _local_rows(rows: np.ndarray, rank: int, a: int, b: int, what: str) -> tuple[int, int]:
+    """Local positions of the global month rows [a, b), which ``rows`` must hold."""
+    la, lb = int(np.searchsorted(rows, a)), int(np.searchsorted(rows, b))
+    if lb - la != b - a:
+        raise ValueError(f"rank {rank}: local months miss the rows [{a}, {b}) of its {what}")
+    return la, lb
 
 
 def rank_years(nY: int, world: int, rank: int) -> np.ndarray:
@@ -330,11 +380,31 @@ class GridResult:
     all_months: np.ndarray | None = None
 
 
+@dataclass(frozen=True, eq=False)
+class SearchSetup:
+    """Everything of a grid search that depends only on its shape (``_search_setup``)."""
+    plan: SearchPlan
+    layout: WinLayout
+    yl: np.ndarray                     # hp-year indices of this rank
+    nYl: int
+    win: WindowPlan
+    cell_src: np.ndarray               # cells [g][year][p]: window row, n = p + 1, 1 / count
+    cell_n: np.ndarray
+    cell_scale: np.ndarray
+    jc: np.ndarray                     # validation jobs [val month][g][p]: cell, month row, n
+    jm: np.ndarray
+    jn: np.ndarray
+    v_yi: np.ndarray                   # local year index and local month row per validation row
+    v_m: np.ndarray
+    nVr: int
+    lvec: torch.Tensor
+
+
 _SETUP: dict = {}
 
 
 def _search_setup(months: np.ndarray, years: np.ndarray, p_vec, G: int, T: int, world: int,
-                  rank: int, dev, l_vec: np.ndarray, rows: np.ndarray) -> dict:
+                  rank: int, dev, l_vec: np.ndarray, rows: np.ndarray) -> SearchSetup:
     """Everything of a grid search that depends only on its shape - the window plan and
     canonical chunk layout, this rank's segments, chunk slots, cells and validation jobs, and
     their device copies - built once per shape and reused by every later search (no host
@@ -347,54 +417,10 @@ def _search_setup(months: np.ndarray, years: np.ndarray, p_vec, G: int, T: int, 
         return hit
     plan = make_plan(months, years)
     lay = win_layout(plan, len(years), world)
-    C = lay.C
+    win = rank_window_plan(plan, lay, world, rank, rows, T, dev)
     yl = rank_years(len(years), world, rank)
     nYl = len(yl)
     nP = len(p_vec)
-
-    def loc(a: int, b: int, what: str) -> tuple[int, int]:
-        la, lb = int(np.searchsorted(rows, a)), int(np.searchsorted(rows, b))
-        if lb - la != b - a:
-            raise ValueError(f"rank {rank}: local months miss the rows [{a}, {b}) of its {what}")
-        return la, lb
-
-    # segments in month order: the owned burn-in pieces (prefix only), then the owned years
-    own = [c for c in range(C) if chunk_owner(c, C, world) == rank]
-    st, sp, chunk_seg = [], [], []                    # chunk_seg: (kind, c, s0, s1)
-    for k in own:
-        a, b = loc(*lay.burn[k], "burn-in piece")
-        chunk_seg.append(("b", k, len(st), len(st) + 1))
-        st.append(a)
-        sp.append(b)
-    skip = len(st)
-    yseg = {}
-    for c in own:
-        s0 = len(st)
-        for y in lay.ychunks[c]:
-            a, b = loc(int(plan.seg_start[y]), int(plan.seg_stop[y]), "window blocks")
-            st.append(a)
-            sp.append(b)
-        chunk_seg.append(("y", c, s0, len(st)))
-        yseg[c] = (s0, len(st))
-    nseg = len(st)
-    # canonical slots of the gathered chunk totals: rank blocks in rank order, each rank's
-    # chunks as listed above (burn pieces, then year chunks, ascending)
-    counts, sb, sy, off = [], [0] * C, [0] * C, 0
-    for r in range(world):
-        ro = [c for c in range(C) if chunk_owner(c, C, world) == r]
-        for i, k in enumerate(ro):
-            sb[k] = off + i
-        for i, c in enumerate(ro):
-            sy[c] = off + len(ro) + i
-        counts.append(2 * len(ro))
-        off += 2 * len(ro)
-    clast = max(own) if nYl else -1
-    ys = [yseg.get(c, (0, 0))[0] for c in range(C)]
-    ye = [yseg.get(c, (0, 0))[1] for c in range(C)]
-    cs = np.asarray([x[2] for x in chunk_seg], np.int32)
-    ce = np.asarray([x[3] for x in chunk_seg], np.int32)
-    slot = np.arange(len(chunk_seg), dtype=np.int32)          # local totals: local order
-    tot_slots = (np.asarray(sb, np.int32), np.asarray(sy, np.int32))
     pv = np.asarray(p_vec, dtype=np.int64)
     gg, yy, pp = np.meshgrid(np.arange(G), np.arange(nYl), np.arange(nP), indexing="ij")
     cell_src = (gg * nYl + yy).reshape(-1)                 # cell order [g][year][p]
@@ -402,8 +428,8 @@ def _search_setup(months: np.ndarray, years: np.ndarray, p_vec, G: int, T: int, 
     cnt = np.maximum(np.asarray(plan.count, dtype=np.int64)[yl], 1) if nYl else np.zeros(0)
     cell_scale = (1.0 / cnt[yy].astype(np.float64)).reshape(-1)
     # validation jobs: [val month][g][p]  -> obj reshapes to [nValLocal, G, nP, L]
-    vrows = ([loc(int(plan.val_start[y]), int(plan.val_stop[y]), "validation halo")
-              for y in yl] if nYl else [])
+    vrows = [_local_rows(rows, rank, int(plan.val_start[y]), int(plan.val_stop[y]),
+                         "validation halo") for y in yl]
     vs = np.asarray([a for a, _ in vrows], np.int64)
     ve = np.asarray([b for _, b in vrows], np.int64)
     nv = ve - vs
@@ -415,56 +441,35 @@ def _search_setup(months: np.ndarray, years: np.ndarray, p_vec, G: int, T: int, 
     jc = ((g2 * nYl + v_yi[vi]) * nP + p2).reshape(-1)
     jm = (g2 * T + v_m[vi]).reshape(-1)
     jn = (pv[p2] + 1).reshape(-1)
-    out = dict(plan=plan, layout=lay, yl=yl, nYl=nYl, st=st, sp=sp, nseg=nseg, skip=skip,
-               cs=cs, ce=ce, slot=slot, sb=tot_slots[0], sy=tot_slots[1],
-               ys=np.asarray(ys, np.int32), ye=np.asarray(ye, np.int32), clast=clast,
-               counts=counts, nlc=len(chunk_seg),
-               cell_src=np.asarray(cell_src), cell_n=np.asarray(cell_n),
-               cell_scale=np.asarray(cell_scale), v_yi=v_yi, v_m=v_m, nVr=nVr,
-               jc=np.asarray(jc), jm=np.asarray(jm), jn=np.asarray(jn), dev_idx=None,
-               lvec=torch.as_tensor(l_vec, dtype=torch.float64, device=dev))
-    # every index the window-sum kernels turn into an address, checked on the host
-    sta, spa = np.asarray(st, np.int64), np.asarray(sp, np.int64)
-    if nseg and (sta.min() < 0 or spa.max() > T or (spa < sta).any() or nseg > 128):
-        raise ValueError(f"rank {rank}: window segments out of range (T={T}, nseg={nseg})")
-    nlc = len(chunk_seg)
-    if nlc and (cs.min() < 0 or ce.max() > nseg or (ce < cs).any()):
-        raise ValueError(f"rank {rank}: chunk segment ranges out of range")
-    nslot = int(sum(counts))
-    for arr in (tot_slots[0], tot_slots[1]):
-        if len(arr) and (arr.min() < 0 or arr.max() >= nslot):
-            raise ValueError(f"rank {rank}: chunk total slots out of range")
-    if nseg and dev is not None and dev.type == "cuda":
-        from ..ops.ridge import upload
-        out["dev_idx"] = upload([np.asarray(st, np.int32), np.asarray(sp, np.int32),
-                                 np.concatenate([cs, ce, slot]).astype(np.int32),
-                                 np.concatenate([out["sb"], out["sy"], out["ys"],
-                                                 out["ye"]]).astype(np.int32)], dev)
+    out = SearchSetup(plan=plan, layout=lay, yl=yl, nYl=nYl, win=win,
+                      cell_src=np.asarray(cell_src), cell_n=np.asarray(cell_n),
+                      cell_scale=np.asarray(cell_scale), jc=np.asarray(jc), jm=np.asarray(jm),
+                      jn=np.asarray(jn), v_yi=v_yi, v_m=v_m, nVr=nVr,
+                      lvec=torch.as_tensor(l_vec, dtype=torch.float64, device=dev))
     if len(_SETUP) > 32:
         _SETUP.clear()
     _SETUP[key] = out
     return out
 
 
-def window_sums(reals: "PfmlReals", su: dict) -> tuple[torch.Tensor, torch.Tensor]:
+def window_sums(reals: "PfmlReals", wp: WindowPlan) -> tuple[torch.Tensor, torch.Tensor]:
     """Expanding-window sums (SD [G, nYl, P, P], Sr [G, nYl, P]) of this rank's hp years in
     the canonical chunk order (see the module docstring): local chunk totals, ONE all-gather
     of them, then the windows.  Device: csrc/segsum.hip (segment sums + totals, windows);
     CPU: the same folds in torch.  At world size one nothing is exchanged, and the device path
     is ONE launch that reads every month once and writes the windows once, bitwise the same
-    (``ops.ridge.window_sums_onepass``; ``PFML_WSUM_ONEPASS=0`` keeps the two-kernel path)."""
-    from ..ops.ridge import chunk_totals, chunk_windows, window_sums_onepass
+    (``ops.wsum.window_sums_onepass``; ``PFML_WSUM_ONEPASS=0`` keeps the two-kernel path)."""
     X, R = reals.denom, reals.r_tilde.contiguous()
     env = dist_env()
     if (X.device.type == "cuda" and R.device.type == "cuda" and env.world_size == 1
             and not env.is_dist and os.environ.get("PFML_WSUM_ONEPASS", "1") != "0"):
-        return window_sums_onepass(X, R, su)
-    totD, totR, scratch = chunk_totals(X, R, su)
+        return window_sums_onepass(X, R, wp)
+    totD, totR, scratch = chunk_totals(X, R, wp)
     if env.is_dist:
         # chunk-major rows [slot][matrix totals | vector totals]: ONE known-size all-gather of
         # every rank's chunk totals (matrices and vectors together)
         G, P = totD.shape[1], totD.shape[-1]
-        tot = coll.all_gather_known(scratch["tot"], [c for c in su["counts"]])
+        tot = coll.all_gather_known(scratch["tot"], list(wp.counts))
         totD = tot[:, :G * P * P].view(-1, G, P, P)
         totR = tot[:, G * P * P:].view(-1, G, P)
     elif env.world_size > 1:
@@ -472,15 +477,15 @@ def window_sums(reals: "PfmlReals", su: dict) -> tuple[torch.Tensor, torch.Tenso
         # are no-ops): the gathered layout with this rank's totals in its own slots and zeros
         # for the other ranks' - the kernels see the real shapes; the sums lack the other
         # ranks' chunks, so only the timing is meaningful
-        off = int(sum(su["counts"][:env.rank]))
-        fullD = torch.zeros((int(sum(su["counts"])),) + tuple(totD.shape[1:]), dtype=totD.dtype,
+        off = int(sum(wp.counts[:env.rank]))
+        fullD = torch.zeros((wp.nslot,) + tuple(totD.shape[1:]), dtype=totD.dtype,
                             device=totD.device)
-        fullR = torch.zeros((int(sum(su["counts"])),) + tuple(totR.shape[1:]), dtype=totR.dtype,
+        fullR = torch.zeros((wp.nslot,) + tuple(totR.shape[1:]), dtype=totR.dtype,
                             device=totR.device)
         fullD[off:off + totD.shape[0]] = totD
         fullR[off:off + totR.shape[0]] = totR
         totD, totR = fullD, fullR
-    return chunk_windows(X, R, su, totD, totR, scratch)
+    return chunk_windows(X, R, wp, totD, totR, scratch)
 
 
 def grid_search(reals: PfmlReals, cfg: Config, *, gather: bool = True) -> GridResult:
@@ -499,27 +504,27 @@ def grid_search(reals: PfmlReals, cfg: Config, *, gather: bool = True) -> GridRe
         raise ValueError("grid_search: local months must be a subset of all_months")
     su = _search_setup(all_months, np.asarray(years), p_vec, G, T, env.world_size, env.rank, dev,
                        np.asarray(cfg.l_vec, dtype=np.float64), rows)
-    lvec = su["lvec"]
+    lvec = su.lvec
     L = lvec.numel()
-    plan, yl, nYl = su["plan"], su["yl"], su["nYl"]
+    yl, nYl = su.yl, su.nYl
 
     # ---- 1. window sums over this rank's chunks (canonical order; one all-gather) -----
     range_push("search.window_sums")
-    SD, Sr = window_sums(reals, su)
+    SD, Sr = window_sums(reals, su.win)
     range_pop()
 
     # ---- 2. ridge grid + 3. utilities for every (cell, validation month) -------------
     th("grid_search.window_sums")
     range_push("search.ridge_utilities")
-    v_yi, v_m = su["v_yi"], su["v_m"]
+    v_yi, v_m = su.v_yi, su.v_m
     th("grid_search.plan")
     # ridge grid + utilities, big-n cells overlapped with the rest on a second stream
     beta, obj = ridge_utilities(SD.reshape(G * nYl, P, P), Sr.reshape(G * nYl, P),
-                                su["cell_src"], su["cell_n"], su["cell_scale"], lvec,
+                                su.cell_src, su.cell_n, su.cell_scale, lvec,
                                 reals.denom.reshape(G * T, P, P),
-                                reals.r_tilde.reshape(G * T, P), su["jc"], su["jm"], su["jn"])
+                                reals.r_tilde.reshape(G * T, P), su.jc, su.jm, su.jn)
     beta = beta.view(G, nYl, nP, L, P)
-    obj = obj.view(su["nVr"], G, nP, L)
+    obj = obj.view(su.nVr, G, nP, L)
     range_pop()
 
     th("grid_search.ridge_utilities")

@@ -11,6 +11,7 @@ import ctypes as C
 import os
 import threading
 
+import numpy as np
 import torch
 
 from .. import build as _build
@@ -43,10 +44,6 @@ def _declare_hip(lib):
     lib.pfml_quadform_row_tiles.restype = I
     lib.pfml_quadform_aligned.argtypes = [I, I, L, L]
     lib.pfml_quadform_aligned.restype = I
-    lib.pfml_segsum.argtypes = [P, L, P, P, I, P, P]
-    lib.pfml_segsum.restype = I
-    lib.pfml_wsum_onepass.argtypes = [P, P, I, I, I, P, P, I, I, I, P, I, P, I, P, P, P]
-    lib.pfml_wsum_onepass.restype = I
     lib.pfml_spd_inverse.argtypes = [P, I, L, L, I, P, P, P]
     lib.pfml_spd_inverse.restype = I
     lib.pfml_spd_inverse_work_doubles.argtypes = [I, I]
@@ -131,6 +128,21 @@ def stream_of(t: torch.Tensor) -> int:
 
 def is_device(t: torch.Tensor) -> bool:
     return t.device.type == "cuda"
+
+
+def upload(arrays, device) -> list[torch.Tensor]:
+    """Copy several small host arrays to the device with ONE pinned, non-blocking H2D copy
+    (the host never waits for queued kernels).  Returns uint8 device views, one per array."""
+    offs, nbytes = [], 0
+    for a in arrays:
+        offs.append(nbytes)
+        nbytes += (a.nbytes + 255) // 256 * 256
+    host = torch.empty(max(nbytes, 1), dtype=torch.uint8, pin_memory=True)
+    hv = host.numpy()
+    for a, o in zip(arrays, offs):
+        hv[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+    dev = host.to(device, non_blocking=True)
+    return [dev[o:o + a.nbytes] for a, o in zip(arrays, offs)]
 
 
 def loaded_libraries() -> list[str]:

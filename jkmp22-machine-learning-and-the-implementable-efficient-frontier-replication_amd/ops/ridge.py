@@ -1,8 +1,9 @@
-"""Hyper-parameter grid kernels: window sums (K14), ridge solves (K15), utilities (K16).
+"""Hyper-parameter grid kernels: ridge solves (K15) and utilities (K16); the window sums
+(K14) are ops/wsum.py.
 
-Device paths run csrc/segsum.hip, csrc/ridge.hip and csrc/quadform.hip; CPU paths are the
-fp64 oracle in the reference's own formulation (np.linalg.solve per lambda,
-PFML_Search_Coef.py:131-133; r'b - 1/2 b'Db per month, PFML_hp_reals.py:94).
+Device paths run csrc/ridge.hip and csrc/quadform.hip; CPU paths are the fp64 oracle in the
+reference's own formulation (np.linalg.solve per lambda, PFML_Search_Coef.py:131-133;
+r'b - 1/2 b'Db per month, PFML_hp_reals.py:94).
 """
 from __future__ import annotations
 
@@ -14,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from ._native import upload      # noqa: F401  (tools and tests spell it ridge.upload)
 
 CELL_DTYPE = np.dtype([("src", "<i8"), ("rsrc", "<i8"), ("work", "<i8"), ("out", "<i8"),
                        ("n", "<i4"), ("_pad", "<i4"), ("scale", "<f8")])
@@ -33,263 +35,6 @@ class LaunchArgs(C.Structure):
 
 nat.register_hip("pfml_ridge_grid", [C.POINTER(LaunchArgs), C.c_void_p])
 nat.register_hip("pfml_ridge_timing_words", [C.c_int], C.c_int64)
-
-
-def segment_sums(X: torch.Tensor, starts, stops, dev_bounds=None) -> torch.Tensor:
-    """out[s] = X[starts[s]:stops[s]].sum(0) for X of shape [T, ...].  ``dev_bounds``:
-    device int32 copies of (starts, stops), e.g. from a cached plan (no host->device copy)."""
-    T = X.shape[0]
-    tail = X.shape[1:]
-    starts = np.asarray(starts, dtype=np.int32)
-    stops = np.asarray(stops, dtype=np.int32)
-    S = len(starts)
-    out = torch.empty((S, *tail), dtype=X.dtype, device=X.device)
-    if nat.is_device(X):
-        if X.dtype != torch.float64 or not X.is_contiguous():
-            raise ValueError("segment_sums: contiguous fp64 required")
-        E = X[0].numel() if T > 0 else int(np.prod(tail))
-        st, sp = dev_bounds if dev_bounds is not None else upload([starts, stops], X.device)
-        nat.check(nat.hip_lib().pfml_segsum(X.data_ptr(), E, st.data_ptr(), sp.data_ptr(), S,
-                                            out.data_ptr(), nat.stream_of(X)), "pfml_segsum")
-    else:
-        for s in range(S):
-            out[s] = X[starts[s]:stops[s]].sum(0)
-    return out
-
-
-nat.register_hip("pfml_window_prefix_vec", [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
-                                            C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p])
-nat.register_hip("pfml_window_prefix_vec_max_segments", [], C.c_int)
-
-
-def window_prefix_vec(X: torch.Tensor, starts, stops, dev_bounds=None,
-                      skip: int = 0) -> torch.Tensor:
-    """out[g, s - skip] = sum of X[g, t] over the months of segments 0..s, for s >= skip (X:
-    [G, T, E], e.g. the r_tilde vectors).  Device: one launch (csrc/segsum.hip); contiguous
-    [G, S - skip, E] output."""
-    G, T, E = X.shape
-    starts = np.asarray(starts, dtype=np.int32)
-    stops = np.asarray(stops, dtype=np.int32)
-    S = len(starts)
-    out = torch.empty((G, max(S - skip, 0), E), dtype=X.dtype, device=X.device)
-    if S - skip <= 0:
-        return out
-    if nat.is_device(X) and S <= nat.hip_lib().pfml_window_prefix_vec_max_segments():
-        if X.dtype != torch.float64 or not X.is_contiguous():
-            raise ValueError("window_prefix_vec: contiguous fp64 required")
-        st, sp = dev_bounds if dev_bounds is not None else upload([starts, stops], X.device)
-        nat.check(nat.hip_lib().pfml_window_prefix_vec(
-            X.data_ptr(), E, T, G, st.data_ptr(), sp.data_ptr(), S, int(skip), out.data_ptr(),
-            nat.stream_of(X)), "pfml_window_prefix_vec")
-        return out
-    acc = torch.zeros((G, E), dtype=X.dtype, device=X.device)
-    for s in range(S):
-        acc = acc + X[:, starts[s]:stops[s]].sum(1)
-        if s >= skip:
-            out[:, s - skip] = acc
-    return out
-
-
-nat.register_hip("pfml_window_prefix_sym", [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                            C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                            C.c_void_p])
-
-
-def window_prefix_sym(X: torch.Tensor, starts, stops, dev_bounds=None,
-                      skip: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
-    """out[g, s - skip] = sum of X[g, t] over the months of segments 0..s, for s >= skip (X:
-    [G, T, P, P], every X[g, t] symmetric; the first ``skip`` segments only feed the prefix).
-    Device: one pass over the upper triangles (csrc/segsum.hip), contiguous output (``out``:
-    a preallocated contiguous [G, S - skip, P, P] destination, e.g. one g's slice)."""
-    G, T, P, _ = X.shape
-    starts = np.asarray(starts, dtype=np.int32)
-    stops = np.asarray(stops, dtype=np.int32)
-    S = len(starts)
-    if out is None:
-        out = torch.empty((G, max(S - skip, 0), P, P), dtype=X.dtype, device=X.device)
-    elif out.shape != (G, max(S - skip, 0), P, P) or not out.is_contiguous():
-        raise ValueError("window_prefix_sym: out must be a contiguous [G, S - skip, P, P] tensor")
-    if S == 0:
-        return out
-    if nat.is_device(X):
-        if X.dtype != torch.float64 or not X.is_contiguous():
-            raise ValueError("window_prefix_sym: contiguous fp64 required")
-        st, sp = dev_bounds if dev_bounds is not None else upload([starts, stops], X.device)
-        scratch = (torch.empty((G, skip, P, P), dtype=X.dtype, device=X.device) if skip
-                   else None)
-        nat.check(nat.hip_lib().pfml_window_prefix_sym(
-            X.data_ptr(), P, T, G, st.data_ptr(), sp.data_ptr(), S, int(skip), out.data_ptr(),
-            scratch.data_ptr() if scratch is not None else None, nat.stream_of(X)),
-            "pfml_window_prefix_sym")
-        return out
-    acc = torch.zeros((G, P, P), dtype=X.dtype)
-    for s in range(S):
-        acc = acc + X[:, starts[s]:stops[s]].sum(1)
-        if s >= skip:
-            out[:, s - skip] = acc
-    return out
-
-
-nat.register_hip("pfml_wsum_chunk_totals", [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                            C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                            C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
-                                            C.c_void_p])
-nat.register_hip("pfml_wsum_chunk_prefix", [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                            C.c_int64, C.c_int, C.c_void_p])
-nat.register_hip("pfml_wvec_chunk", [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
-                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                     C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
-                                     C.c_void_p, C.c_void_p])
-
-
-def _fold_months(X: torch.Tensor, a: int, b: int) -> torch.Tensor:
-    """CPU segment sum: left fold over months a .. b-1 of X [G, T, ...] (a fixed order, the
-    same on every rank that holds these months)."""
-    acc = torch.zeros_like(X[:, 0])
-    for t in range(a, b):
-        acc = acc + X[:, t]
-    return acc
-
-
-def chunk_totals(X: torch.Tensor, R: torch.Tensor, su: dict):
-    """Kernel A of the canonical chunked window sums (models/search.py): segment sums of this
-    rank's segments and the totals of its chunks, chunk-major [nlc, G, P, P] / [nlc, G, P].
-    Returns (totD, totR, bufs); ``bufs`` carries the segment sums to ``chunk_windows``."""
-    G, T, P, _ = X.shape
-    nlc, nseg, skip, nYl = su["nlc"], su["nseg"], su["skip"], su["nYl"]
-    # matrix and vector totals of a chunk side by side in ONE row of one buffer (``bufs["tot"]``,
-    # [nlc, G P P + G P]): the multi-rank path all-gathers them as one collective; totD / totR
-    # are row-strided views and the kernels take that row stride
-    GPP = G * P * P
-    tot = torch.empty((nlc, GPP + G * P), dtype=X.dtype, device=X.device)
-    totD = tot[:, :GPP].view(nlc, G, P, P)
-    totR = tot[:, GPP:].view(nlc, G, P)
-    out = torch.empty((G, nYl, P, P), dtype=X.dtype, device=X.device)
-    if nat.is_device(X):
-        if X.dtype != torch.float64 or not X.is_contiguous():
-            raise ValueError("chunk_totals: contiguous fp64 required")
-        scratch = (torch.empty((G, skip, P, P), dtype=X.dtype, device=X.device) if skip
-                   else None)
-        st, sp, idx, cidx = su["dev_idx"]
-        lib = nat.hip_lib()
-        s = nat.stream_of(X)
-        nat.check(lib.pfml_wsum_chunk_totals(
-            X.data_ptr(), P, T, G, st.data_ptr(), sp.data_ptr(), nseg, skip, out.data_ptr(),
-            scratch.data_ptr() if scratch is not None else None, nlc, idx.data_ptr(),
-            totD.data_ptr(), totD.stride(0), s), "pfml_wsum_chunk_totals")
-        nat.check(lib.pfml_wvec_chunk(
-            R.data_ptr(), P, T, G, st.data_ptr(), sp.data_ptr(), nseg, skip, 0, nlc,
-            idx.data_ptr(), su["layout"].C, cidx.data_ptr(), su["clast"], totR.data_ptr(),
-            totR.stride(0), None, s), "pfml_wvec_chunk")
-        return totD, totR, {"out": out, "scratch": scratch, "tot": tot}
-    segD = [_fold_months(X, a, b) for a, b in zip(su["st"], su["sp"])]
-    segR = [_fold_months(R, a, b) for a, b in zip(su["st"], su["sp"])]
-    for lc in range(nlc):
-        accD, accR = torch.zeros_like(X[:, 0]), torch.zeros_like(R[:, 0])
-        for s in range(int(su["cs"][lc]), int(su["ce"][lc])):
-            accD = accD + segD[s]
-            accR = accR + segR[s]
-        totD[lc], totR[lc] = accD, accR
-    return totD, totR, {"out": out, "segD": segD, "segR": segR, "tot": tot}
-
-
-def chunk_windows(X: torch.Tensor, R: torch.Tensor, su: dict, totD: torch.Tensor,
-                  totR: torch.Tensor, bufs: dict) -> tuple[torch.Tensor, torch.Tensor]:
-    """Kernel B of the canonical chunked window sums: E = fold of the burn-in totals, then per
-    year chunk the fold of its segments from the prefix P_c (``totD``/``totR``: every chunk's
-    total, gathered, in the canonical slot order of ``su``).  Returns (SD, Sr)."""
-    G, T, P, _ = X.shape
-    nseg, skip, nYl, clast = su["nseg"], su["skip"], su["nYl"], su["clast"]
-    C = su["layout"].C
-    out = bufs["out"]
-    nslot = int(sum(su["counts"]))
-    if totD.shape[0] != nslot or totR.shape[0] != nslot:
-        # the slot map addresses the GATHERED totals of every rank (a local-only buffer here
-        # would be read out of bounds by the device kernels)
-        raise ValueError(f"chunk_windows: {totD.shape[0]} chunk totals, the canonical layout "
-                         f"has {nslot} slots (all-gather missing?)")
-    Sr = torch.empty((G, nYl, P), dtype=X.dtype, device=X.device)
-    if nat.is_device(X):
-        st, sp, idx, cidx = su["dev_idx"]
-        lib = nat.hip_lib()
-        s = nat.stream_of(X)
-        scratch = bufs["scratch"]
-        # (row-strided totals: each slot's G blocks contiguous, the slots totD.stride(0) apart)
-        if totD.stride()[1:] != (P * P, P, 1) or totR.stride()[1:] != (P, 1):
-            raise ValueError("chunk_windows: chunk totals must be row-strided [slot][g] blocks")
-        nat.check(lib.pfml_wsum_chunk_prefix(
-            P, G, nseg, skip, out.data_ptr(), scratch.data_ptr() if scratch is not None else None,
-            C, cidx.data_ptr(), totD.data_ptr(), totD.stride(0), clast, s),
-            "pfml_wsum_chunk_prefix")
-        nat.check(lib.pfml_wvec_chunk(
-            R.data_ptr(), P, T, G, st.data_ptr(), sp.data_ptr(), nseg, skip, 1, 0,
-            idx.data_ptr(), C, cidx.data_ptr(), clast, totR.data_ptr(), totR.stride(0),
-            Sr.data_ptr(), s), "pfml_wvec_chunk")
-        return out, Sr
-    segD, segR = bufs["segD"], bufs["segR"]
-    pD, pR = torch.zeros_like(X[:, 0]), torch.zeros_like(R[:, 0])
-    for k in range(C):
-        pD = pD + totD[int(su["sb"][k])]
-        pR = pR + totR[int(su["sb"][k])]
-    for c in range(clast + 1):
-        aD, aR = pD, pR
-        for s in range(int(su["ys"][c]), int(su["ye"][c])):
-            aD = aD + segD[s]
-            aR = aR + segR[s]
-            if s >= skip:
-                out[:, s - skip] = aD
-                Sr[:, s - skip] = aR
-        if c < clast:
-            pD = pD + totD[int(su["sy"][c])]
-            pR = pR + totR[int(su["sy"][c])]
-    return out, Sr
-
-
-def window_sums_onepass(X: torch.Tensor, R: torch.Tensor, su: dict):
-    """The canonical chunked window sums of a rank that owns every chunk (world size one) in
-    ONE launch (csrc/segsum.hip wsum_onepass_kernel): each month's upper triangle is read once
-    and the windows are written once, with no segment sums or chunk totals in memory.  Bitwise
-    ``chunk_windows(*chunk_totals(...))``.  Returns (SD [G, nYl, P, P], Sr [G, nYl, P])."""
-    G, T, P, _ = X.shape
-    nlc, nseg, skip, nYl, clast = su["nlc"], su["nseg"], su["skip"], su["nYl"], su["clast"]
-    C = su["layout"].C
-    if not nat.is_device(X) or not nat.is_device(R):
-        raise ValueError("window_sums_onepass: device tensors required")
-    if X.dtype != torch.float64 or not X.is_contiguous():
-        raise ValueError("window_sums_onepass: contiguous fp64 required")
-    if R.dtype != torch.float64 or not R.is_contiguous() or R.shape != (G, T, P):
-        raise ValueError("window_sums_onepass: R must be a contiguous fp64 [G, T, P] tensor")
-    if su.get("onepass_T") != T:
-        # the kernel walks each element's months once, in canonical order: every chunk is
-        # local, its total sits in its own slot, a year chunk's total folds the segments of
-        # its windows and the canonical walk visits the segments in index order (checked once
-        # per cached layout)
-        nslot = int(sum(su["counts"]))
-        cs, ce = np.asarray(su["cs"]), np.asarray(su["ce"])
-        sy = np.asarray(su["sy"])[:clast + 1]
-        sb = np.asarray(su["sb"])
-        walk = ([s for k in range(C) if sb[k] < nlc for s in range(cs[sb[k]], ce[sb[k]])]
-                + [s for c in range(clast + 1) for s in range(su["ys"][c], su["ye"][c])])
-        if (nlc != nslot or nlc != 2 * C or nYl != nseg - skip or walk != list(range(nseg))
-                or not np.array_equal(su["slot"], np.arange(nlc))
-                or not np.array_equal(cs[sy], np.asarray(su["ys"])[:clast + 1])
-                or not np.array_equal(ce[sy], np.asarray(su["ye"])[:clast + 1])):
-            raise ValueError("window_sums_onepass: this rank does not own every chunk of the "
-                             "canonical layout (world size one required)")
-        if int(np.max(su["sp"], initial=0)) > T or int(np.min(su["st"], initial=0)) < 0:
-            raise ValueError("window_sums_onepass: window segments out of range")
-        su["onepass_T"] = T
-    SD = torch.empty((G, nYl, P, P), dtype=X.dtype, device=X.device)
-    Sr = torch.empty((G, nYl, P), dtype=X.dtype, device=X.device)
-    if nYl == 0 or nseg == 0:
-        return SD, Sr
-    st, sp, idx, cidx = su["dev_idx"]
-    nat.check(nat.hip_lib().pfml_wsum_onepass(
-        X.data_ptr(), R.data_ptr(), P, T, G, st.data_ptr(), sp.data_ptr(), nseg, skip, nlc,
-        idx.data_ptr(), C, cidx.data_ptr(), clast, SD.data_ptr(), Sr.data_ptr(),
-        nat.stream_of(X)), "pfml_wsum_onepass")
-    return SD, Sr
 
 
 class _HostClock:
@@ -315,21 +60,6 @@ class _HostClock:
             now = self.time()
             print(f"[host] {what}: {1e6 * (now - self.t):.0f} us", file=sys.stderr)
             self.t = now
-
-
-def upload(arrays, device) -> list[torch.Tensor]:
-    """Copy several small host arrays to the device with ONE pinned, non-blocking H2D copy
-    (the host never waits for queued kernels).  Returns uint8 device views, one per array."""
-    offs, nbytes = [], 0
-    for a in arrays:
-        offs.append(nbytes)
-        nbytes += (a.nbytes + 255) // 256 * 256
-    host = torch.empty(max(nbytes, 1), dtype=torch.uint8, pin_memory=True)
-    hv = host.numpy()
-    for a, o in zip(arrays, offs):
-        hv[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-    dev = host.to(device, non_blocking=True)
-    return [dev[o:o + a.nbytes] for a, o in zip(arrays, offs)]
 
 
 _WORK_CACHE: dict = {}
@@ -371,7 +101,7 @@ class Switches:
     bt_wy          n > 1024 cells on the blocked-WY MFMA back-transform; PFML_RIDGE_BT_WY=0: generic
     two_streams    the largest cells' group and the rest on two streams; PFML_RIDGE_STREAMS=1: one
     quad_direct    the pipelined utilities form; PFML_QUAD_DIRECT not empty: the direct-A form
-    quad_xcd       every utilities tile of a cell on one XCD (``_xcd_affine``); PFML_QUAD_XCD=0: not
+    quad_xcd       every utilities tile of a cell on one XCD (``_xcd_order``); PFML_QUAD_XCD=0: not
 
     PFML_RIDGE_STREAMS means one stream at any value but empty or 2.  Retired, ValueError both:
     PFML_QUAD_DIRECT=0, PFML_QUAD_MM=2 - the removed LDS-staged forms (PFML_QUAD_MM=1: a no-op).
@@ -1040,12 +770,6 @@ def _xcd_order(cell: np.ndarray) -> np.ndarray:
         order[s] = queues[k][heads[k]]
         heads[k] += 1
     return order
-
-
-def _xcd_affine(jobs_t: np.ndarray, rt: np.ndarray, cell: np.ndarray):
-    """``_xcd_order`` applied to a launch's single tiles."""
-    order = _xcd_order(cell)
-    return jobs_t[order], rt[order]
 
 
 def quad_launch(plan: dict, d_desc: torch.Tensor, d_tj: torch.Tensor, D: torch.Tensor,

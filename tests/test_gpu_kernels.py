@@ -317,18 +317,6 @@ def test_spd_inverse_sym_out_of_place_bitwise(gpu, n):
     assert torch.equal(out[:4], inplace[:4])
 
 
-def test_segment_sums(gpu):
-    from pfml.ops.ridge import segment_sums
-    X = _rand(40, 7, 9, seed=7)
-    st, sp = [0, 5, 5, 20], [5, 5, 20, 40]
-    ref = segment_sums(X, st, sp)
-    out = segment_sums(X.to(gpu), st, sp).cpu()
-    assert torch.allclose(out, ref, rtol=1e-14, atol=1e-13)
-    Y = _rand(11, 6, seed=8)   # even row length -> vector path
-    assert torch.allclose(segment_sums(Y.to(gpu), [0, 3], [3, 11]).cpu(),
-                          segment_sums(Y, [0, 3], [3, 11]), rtol=1e-14, atol=1e-13)
-
-
 def _spd_stack(S, P, n_obs=40, seed=0):
     X = _rand(S, n_obs, P, seed=seed)
     return X.transpose(1, 2) @ X
@@ -664,46 +652,6 @@ def test_gemm_lowp(gpu, fmt, ta, tb):
     assert (out - exact).abs().max().item() / scale < (1e-2 if fmt == "bf16" else 1e-1)
 
 
-def test_window_prefix_vec(gpu):
-    """One-launch expanding-window sums of month vectors (r_tilde), incl. gaps and skip."""
-    from pfml.ops.ridge import window_prefix_vec
-    X = _rand(2, 40, 513, seed=83)
-    for st, sp, skip in (([0, 7, 9, 20], [7, 9, 20, 40], 0), ([0, 10, 11], [5, 11, 40], 1)):
-        ref = window_prefix_vec(X, st, sp, skip=skip)
-        got = window_prefix_vec(X.to(gpu), st, sp, skip=skip).cpu()
-        assert got.shape == ref.shape and got.is_contiguous()
-        assert torch.allclose(got, ref, rtol=1e-13, atol=1e-13)
-
-
-def test_window_prefix_sym(gpu):
-    """Fused expanding-window sums over the upper triangles of symmetric month matrices."""
-    from pfml.ops.ridge import window_prefix_sym
-    X = _rand(2, 40, 37, 37, seed=81)
-    X = X + X.transpose(-1, -2)
-    st, sp = [0, 7, 9, 20], [7, 9, 20, 40]
-    ref = window_prefix_sym(X, st, sp)
-    out = window_prefix_sym(X.to(gpu), st, sp).cpu()
-    assert torch.allclose(out, ref, rtol=1e-13, atol=1e-12)
-    assert torch.equal(out, out.transpose(-1, -2))
-    gap_st, gap_sp = [0, 10], [5, 40]          # months 5..9 belong to no segment
-    ref2 = window_prefix_sym(X, gap_st, gap_sp)
-    assert torch.allclose(window_prefix_sym(X.to(gpu), gap_st, gap_sp).cpu(), ref2,
-                          rtol=1e-13, atol=1e-12)
-    for skip in (1, 2):                         # prefix-only leading segments
-        got = window_prefix_sym(X.to(gpu), st, sp, skip=skip).cpu()
-        assert got.shape == (2, 4 - skip, 37, 37) and got.is_contiguous()
-        assert torch.allclose(got, ref[:, skip:], rtol=1e-13, atol=1e-12)
-        assert torch.equal(got, got.transpose(-1, -2))
-    for P in (64, 513):                         # even P; P + 1 > 512 (three entries per lane)
-        Y = _rand(1, 12, P, P, seed=82 + P)
-        Y = Y + Y.transpose(-1, -2)
-        st2, sp2 = [0, 2, 5, 11], [2, 5, 11, 12]
-        ref3 = window_prefix_sym(Y, st2, sp2, skip=1)
-        got = window_prefix_sym(Y.to(gpu), st2, sp2, skip=1).cpu()
-        assert torch.allclose(got, ref3, rtol=1e-13, atol=1e-12)
-        assert torch.equal(got, got.transpose(-1, -2))
-
-
 @pytest.mark.parametrize("compat", [True, False])
 def test_validation_scores_kernel(gpu, compat):
     """csrc/scores.hip (prefix mean + per-month dense rank) vs the torch path on CPU, incl.
@@ -830,7 +778,7 @@ def _chunked_windows_all_ranks(X, R, months, years, W, dev):
     each rank's chunk totals (its local months only), concatenated in canonical slot order,
     then each rank's windows.  Returns {global hp-year index: (SD, Sr)}."""
     from pfml.models.search import _search_setup, local_month_rows
-    from pfml.ops.ridge import chunk_totals, chunk_windows
+    from pfml.ops.wsum import chunk_totals, chunk_windows
     G, T, P, _ = X.shape
     lv = np.array([0.0, 1.0])
     sus, tots = [], []
@@ -840,15 +788,15 @@ def _chunked_windows_all_ranks(X, R, months, years, W, dev):
         Rr = R[:, rows].contiguous().to(dev)
         su = _search_setup(months, years, [16], G, len(rows), W, r,
                            torch.device(dev) if dev != "cpu" else None, lv, rows)
-        totD, totR, bufs = chunk_totals(Xr, Rr, su)
+        totD, totR, bufs = chunk_totals(Xr, Rr, su.win)
         sus.append((su, Xr, Rr, bufs))
         tots.append((totD, totR))
     allD = torch.cat([t[0] for t in tots])
     allR = torch.cat([t[1] for t in tots])
     out = {}
     for su, Xr, Rr, bufs in sus:
-        SD, Sr = chunk_windows(Xr, Rr, su, allD, allR, bufs)
-        for k, y in enumerate(su["yl"]):
+        SD, Sr = chunk_windows(Xr, Rr, su.win, allD, allR, bufs)
+        for k, y in enumerate(su.yl):
             out[int(y)] = (SD[:, k].cpu(), Sr[:, k].cpu())
     return out
 
@@ -883,6 +831,33 @@ def test_chunked_window_sums_world_bitwise(gpu):
         for y in ref:
             assert torch.equal(got[y][0], ref[y][0]), (W, y)
             assert torch.equal(got[y][1], ref[y][1]), (W, y)
+
+
+@pytest.mark.parametrize("P", [64, 513])
+def test_chunked_window_sums_wide(gpu, P):
+    """The chunk path against the CPU folds at even P (64) and at P = 513 - three entries per
+    lane of wsum_upper_kernel's j += 256 loop, nine column blocks of the vector kernel with the
+    last one ragged - at small depth (G = 1, 40 months, 2 hp years); the windows are symmetric
+    and a 2-rank sharding is BITWISE the 1-rank result."""
+    from pfml.utils.dates import mi_from_ym
+    months = np.arange(mi_from_ym(1996, 0), mi_from_ym(1999, 3) + 1, dtype=np.int64)
+    years = np.arange(1998, 2000)
+    assert len(months) == 40
+    X = _rand(1, len(months), P, P, seed=82 + P)
+    X = X + X.transpose(-1, -2)
+    R = _rand(1, len(months), P, seed=83 + P)
+    ref = _chunked_windows_all_ranks(X, R, months, years, 1, gpu)
+    cpu = _chunked_windows_all_ranks(X, R, months, years, 1, "cpu")
+    assert sorted(ref) == sorted(cpu) == list(range(len(years)))
+    for y in ref:
+        assert torch.allclose(ref[y][0], cpu[y][0], rtol=1e-13, atol=1e-12)
+        assert torch.allclose(ref[y][1], cpu[y][1], rtol=1e-13, atol=1e-13)
+        assert torch.equal(ref[y][0], ref[y][0].transpose(-1, -2))
+    got = _chunked_windows_all_ranks(X, R, months, years, 2, gpu)
+    assert sorted(got) == sorted(ref)
+    for y in ref:
+        assert torch.equal(got[y][0], ref[y][0]), y
+        assert torch.equal(got[y][1], ref[y][1]), y
 
 
 def test_quadform_default_equals_direct_odd_jobs(gpu, monkeypatch):

@@ -36,15 +36,15 @@ def _inputs(G, T, P, dev, seed):
 
 
 def _two_kernel(X, R, su):
-    from pfml.ops.ridge import chunk_totals, chunk_windows
-    totD, totR, bufs = chunk_totals(X, R, su)
-    return chunk_windows(X, R, su, totD, totR, bufs)
+    from pfml.ops.wsum import chunk_totals, chunk_windows
+    totD, totR, bufs = chunk_totals(X, R, su.win)
+    return chunk_windows(X, R, su.win, totD, totR, bufs)
 
 
 def _check_bitwise(X, R, su):
-    from pfml.ops.ridge import window_sums_onepass
+    from pfml.ops.wsum import window_sums_onepass
     refD, refR = _two_kernel(X, R, su)
-    SD, Sr = window_sums_onepass(X, R, su)
+    SD, Sr = window_sums_onepass(X, R, su.win)
     assert SD.shape == refD.shape and Sr.shape == refR.shape
     assert torch.equal(Sr, refR)
     assert torch.equal(SD, refD)
@@ -100,7 +100,7 @@ def test_onepass_burn_in_lengths(gpu, case):
     else:
         assert 0 in lens and all(n % 4 for n in lens if n)
     su = _setup(months, years, 2, gpu)
-    assert any(int(a) == int(b) for a, b in zip(su["ys"], su["ye"]))
+    assert any(int(a) == int(b) for a, b in zip(su.win.ys, su.win.ye))
     X, R = _inputs(2, len(months), 45, gpu, 7)
     _check_bitwise(X, R, su)
 
@@ -113,9 +113,9 @@ def test_onepass_trailing_validation_months(gpu):
     months, years = _span(1988, 2, 2004, 7), np.arange(1995, 2004)
     su = _setup(months, years, 2, gpu)
     s1 = _setup(MONTHS1, YEARS1, 2, gpu)
-    assert su["nYl"] == 9 and su["nseg"] - su["skip"] == 9 and s1["nYl"] == 14
-    assert int(max(su["sp"])) < len(months)          # trailing months outside every segment
-    assert su["clast"] == su["layout"].C - 1
+    assert su.nYl == 9 and su.win.nseg - su.win.skip == 9 and s1.nYl == 14
+    assert int(max(su.win.sp)) < len(months)          # trailing months outside every segment
+    assert su.win.clast == su.layout.C - 1
     X, R = _inputs(2, len(months), 37, gpu, 11)
     _check_bitwise(X, R, su)
 
@@ -130,7 +130,7 @@ def case97(gpu):
 def test_onepass_writes_every_element(gpu, case97, monkeypatch):
     """SD and Sr allocated full of NaN: the result has none and is symmetric, so every element
     is stored, the mirrored half and the ragged last tile (P = 97 = 64 + 33) included."""
-    from pfml.ops import ridge
+    from pfml.ops import wsum
     su, X, R = case97
     real_empty = torch.empty
 
@@ -138,8 +138,8 @@ def test_onepass_writes_every_element(gpu, case97, monkeypatch):
         t = real_empty(*a, **k)
         return t.fill_(float("nan")) if t.is_floating_point() else t
 
-    monkeypatch.setattr(ridge.torch, "empty", nan_empty)
-    SD, Sr = ridge.window_sums_onepass(X, R, su)
+    monkeypatch.setattr(wsum.torch, "empty", nan_empty)
+    SD, Sr = wsum.window_sums_onepass(X, R, su.win)
     monkeypatch.undo()
     assert not torch.isnan(SD).any() and not torch.isnan(Sr).any()
     assert torch.equal(SD, SD.transpose(-1, -2))
@@ -150,13 +150,13 @@ def test_onepass_writes_every_element(gpu, case97, monkeypatch):
 def test_onepass_never_reads_lower_triangle(gpu, case97):
     """The strict lower triangle of every month set to NaN: bitwise the symmetric input's
     result."""
-    from pfml.ops.ridge import window_sums_onepass
+    from pfml.ops.wsum import window_sums_onepass
     su, X, R = case97
     P = X.shape[-1]
     low = torch.ones(P, P, dtype=torch.bool, device=gpu).tril(-1)
     Xn = X.masked_fill(low, float("nan"))
-    SD, Sr = window_sums_onepass(X, R, su)
-    SDn, Srn = window_sums_onepass(Xn, R, su)
+    SD, Sr = window_sums_onepass(X, R, su.win)
+    SDn, Srn = window_sums_onepass(Xn, R, su.win)
     assert torch.equal(SDn, SD) and torch.equal(Srn, Sr)
 
 
@@ -206,11 +206,11 @@ def test_onepass_switch(gpu, monkeypatch):
     assert search.dist_env().world_size == 1
     seen = _spy(monkeypatch, ENTRY)
     monkeypatch.delenv("PFML_WSUM_ONEPASS", raising=False)
-    SD1, Sr1 = search.window_sums(reals, su)
+    SD1, Sr1 = search.window_sums(reals, su.win)
     assert seen == ["pfml_wsum_onepass"]
     del seen[:]
     monkeypatch.setenv("PFML_WSUM_ONEPASS", "0")
-    SD0, Sr0 = search.window_sums(reals, su)
+    SD0, Sr0 = search.window_sums(reals, su.win)
     assert "pfml_wsum_onepass" not in seen
     assert {"pfml_wsum_chunk_totals", "pfml_wsum_chunk_prefix"} <= set(seen)
     assert torch.equal(SD1, SD0) and torch.equal(Sr1, Sr0)
@@ -223,6 +223,6 @@ def test_onepass_switch(gpu, monkeypatch):
                               denom=X[:, rows].contiguous(), all_months=months)
     monkeypatch.setattr(search, "dist_env",
                         lambda: types.SimpleNamespace(world_size=2, rank=0, is_dist=False))
-    search.window_sums(reals2, su2)
+    search.window_sums(reals2, su2.win)
     assert "pfml_wsum_onepass" not in seen
     assert {"pfml_wsum_chunk_totals", "pfml_wsum_chunk_prefix"} <= set(seen)

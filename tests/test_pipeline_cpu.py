@@ -288,6 +288,29 @@ def test_validation_scores_nan_semantics_cpu():
                           np.nan_to_num(exp_r, nan=-1))
 
 
+def test_window_plan_frozen_and_onepass_decided_at_construction():
+    """The window plan of a search setup is immutable, and its one-pass eligibility is settled
+    when it is built: a world-1 rank owns every chunk, rank 0 of a 2-rank run does not."""
+    import dataclasses
+    from pfml.models.search import _search_setup, local_month_rows
+    from pfml.utils.dates import mi_from_ym
+    months = np.arange(mi_from_ym(1990, 0), mi_from_ym(2012, 11) + 1, dtype=np.int64)
+    years = np.arange(1998, 2012)
+    lv = np.array([0.0, 1.0])
+    su = _search_setup(months, years, [16], 2, len(months), 1, 0, None, lv,
+                       np.arange(len(months)))
+    assert su.win.onepass is True and su.win.T == len(months)
+    with pytest.raises(dataclasses.FrozenInstanceError):
+        su.win.onepass = False
+    with pytest.raises(dataclasses.FrozenInstanceError):
+        su.win.nseg = 0
+    with pytest.raises(dataclasses.FrozenInstanceError):
+        su.win = None
+    rows = local_month_rows(months, years, 2, 0)
+    su2 = _search_setup(months, years, [16], 2, len(rows), 2, 0, None, lv, rows)
+    assert su2.win.onepass is False
+
+
 def test_estimate_cov_batched_matches_pandas_form(small_data):
     """S3 batched form (integer-key merges, segmented z-score / medians, no per-month loop)
     equals the pandas-bound form (groupby lambdas, frame merges, month loop)."""

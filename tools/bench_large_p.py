@@ -71,16 +71,16 @@ def kernel_split(reals, cfg) -> dict:
     months = np.asarray(reals.months, dtype=np.int64)
     su = _search_setup(months, np.asarray(cfg.hp_years), cfg.p_vec, G, T, 1, 0, dev,
                        np.asarray(cfg.l_vec, dtype=np.float64), np.arange(T, dtype=np.int64))
-    SD, Sr = window_sums(reals, su)
-    nYl = su["nYl"]
+    SD, Sr = window_sums(reals, su.win)
+    nYl = su.nYl
     SD, Sr = SD.reshape(G * nYl, P, P), Sr.reshape(G * nYl, P)
     D, R = reals.denom.reshape(G * T, P, P), reals.r_tilde.reshape(G * T, P).contiguous()
-    lv = su["lvec"]
+    lv = su.lvec
     L = int(lv.numel())
-    plan = rg._utilities_plan(P, L, dev, su["cell_src"], su["cell_n"], su["cell_scale"],
-                              su["jc"], su["jm"], su["jn"], split=True)
-    beta = torch.empty((len(su["cell_n"]), L, P), dtype=torch.float64, device=dev)
-    obj = torch.empty((len(su["jc"]), L), dtype=torch.float64, device=dev)
+    plan = rg._utilities_plan(P, L, dev, su.cell_src, su.cell_n, su.cell_scale,
+                              su.jc, su.jm, su.jn, split=True)
+    beta = torch.empty((len(su.cell_n), L, P), dtype=torch.float64, device=dev)
+    obj = torch.empty((len(su.jc), L), dtype=torch.float64, device=dev)
     out = {"band_launch": 0.0, "tridiagonalisation": 0.0, "tridiagonal_solves": 0.0,
            "back_transform": 0.0, "repair": 0.0, "utilities": 0.0, "groups": []}
     dv = plan["dv"]
