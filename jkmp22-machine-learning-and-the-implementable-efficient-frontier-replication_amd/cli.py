@@ -16,6 +16,12 @@ generation and the headline benchmark.
                    theme of characteristics permuted within every OOS month, per theme and
                    draw -> fi.csv, fi_pf.csv, plots/feature_importance.png; same inputs as
                    pfml-ef; one process; not part of `main`)
+    python -m pfml pfml-bmk     --data-dir Data --device cuda
+                   [--set bmk.static.k=[1,0.333,0.2] --set bmk.static.u=[0.25,0.5,1]
+                    --set bmk.static.g=[0,1,2]]
+                   (benchmark portfolios: Portfolio-ML next to Markowitz-ML, the Static-ML
+                   arms, minimum variance and 1/N -> bmk.csv, bmk_pf.csv, bmk_hps.csv,
+                   plots/benchmarks.png; same inputs as pfml-ef; one process; not part of `main`)
     python -m pfml stages a,b,c  (several stages in one process)
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m pfml main ...   (RCCL, one rank/GPU)
 
@@ -29,7 +35,7 @@ import json
 import sys
 
 from .config import Config
-from .pipeline import ALL_STAGES, MAIN_STAGES, Pipeline
+from .pipeline import ALL_STAGES, MAIN_STAGES, SIDE_STAGES, Pipeline
 
 
 def _cfg(a) -> Config:
@@ -52,7 +58,8 @@ def _cfg(a) -> Config:
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="pfml", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("command", help="main | stages | synth-data | " + " | ".join(ALL_STAGES))
+    ap.add_argument("command", help="main | stages | synth-data | "
+                    + " | ".join(ALL_STAGES + SIDE_STAGES))
     ap.add_argument("stages", nargs="?", default=None, help="comma list for `stages`")
     ap.add_argument("--data-dir", default=None)
     ap.add_argument("--artifact-dir", default=None)
@@ -80,7 +87,7 @@ def main(argv=None) -> int:
         stages = MAIN_STAGES
     elif a.command == "stages":
         stages = [s.strip() for s in (a.stages or "").split(",") if s.strip()]
-    elif a.command in ALL_STAGES:
+    elif a.command in ALL_STAGES + SIDE_STAGES:
         stages = [a.command]
     else:
         ap.error(f"unknown command {a.command}")

@@ -140,6 +140,11 @@ def _reference_settings() -> dict:
         # feature-theme importance (models/importance.py): permutation draws per theme, the
         # permutation seed (None: seed_no), the themes (None: every cluster of the labels)
         "fi": {"n_draws": 1, "seed": None, "clusters": None},
+        # benchmark portfolios (models/benchmarks.py): the prediction model's grid (None:
+        # settings["rff"]["l_vec"], pf_ml's p_vec) and the Static-ML arms (k, u, g lists; the
+        # reference's pf.hps.static lists can be passed with --set)
+        "bmk": {"l_vec": None, "p_vec": None,
+                "static": {"k": [1.0], "u": [1.0], "g": [0.0]}},
         "cov_set": {
             "industries": True,
             "obs": 252 * 10,
@@ -302,10 +307,12 @@ class Config:
         """Stable hash of (a subset of) the config, used to key stage artifacts."""
         doc = self.to_jsonable()
         # the whole-config hash keys the stages without a dependency list (and, chained,
-        # everything after them): settings["fi"] is read by pfml-fi alone, which names it, and
-        # stays out, so the keys of every other stage are what they were before it existed
+        # everything after them): settings["fi"] is read by pfml-fi alone and settings["bmk"] by
+        # pfml-bmk alone, which name them, and stay out, so the keys of every other stage are
+        # what they were before those stages existed
         if not sections:
-            doc["settings"] = {k: v for k, v in doc["settings"].items() if k != "fi"}
+            doc["settings"] = {k: v for k, v in doc["settings"].items()
+                               if k not in ("fi", "bmk")}
         if sections:
             doc = {s: doc["settings"].get(s, doc["pf_set"].get(s, doc["run"].get(s)))
                    for s in sections}

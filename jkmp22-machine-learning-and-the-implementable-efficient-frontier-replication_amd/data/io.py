@@ -28,6 +28,10 @@ CSV_COLUMNS = {
                "turnover_notional", "r", "sd", "sr_gross", "tc", "r_tc", "sr", "obj", "obj_drop",
                "reason"],
     "fi_pf.csv": ["cluster", "draw", "inv", "shorting", "turnover", "r", "tc", "eom_ret"],
+    "bmk.csv": ["type", "k", "u", "g", "n", "inv", "shorting", "turnover_notional", "r", "sd",
+                "sr_gross", "tc", "r_tc", "sr", "obj", "reason"],
+    "bmk_pf.csv": ["type", "k", "u", "g", "inv", "shorting", "turnover", "r", "tc", "eom_ret"],
+    "bmk_hps.csv": ["hp_year", "g", "p", "l", "lambda", "val_mse"],
 }
 
 

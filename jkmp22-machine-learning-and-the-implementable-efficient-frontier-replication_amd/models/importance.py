@@ -160,12 +160,6 @@ def _chain_arms(mt_all, a_all, wa, layout: dict, to=None):
     return (Wst, Wopt) if to is None else (Wst.to(to), Wopt.to(to))
 
 
-def _finite_arms(Wst: torch.Tensor, live: torch.Tensor) -> torch.Tensor:
-    """[A] bool: every live w_start of the arm is finite."""
-    z = torch.zeros((), dtype=Wst.dtype, device=Wst.device)
-    return torch.isfinite(torch.where(live, Wst, z)).flatten(1).all(1)
-
-
 def feature_importance(cfg: Config, chars: pd.DataFrame, barra: BarraCov, wealth: pd.DataFrame,
                        risk_free: pd.DataFrame, labels: pd.DataFrame | None, device,
                        n_draws: int | None = None, seed: int | None = None, clusters=None,
@@ -248,14 +242,14 @@ def feature_importance(cfg: Config, chars: pd.DataFrame, barra: BarraCov, wealth
         Wst[A - 1, B // 2, 0] = float("nan")
         COUNTERS.add("fault_injected")
     reasons = [""] * A
-    bad = torch.nonzero(~_finite_arms(Wst, live)).flatten()
+    bad = torch.nonzero(~portfolio.finite_arms(Wst, live)).flatten()
     if bad.numel():
         names = [f"{arms[k][0]}/{arms[k][1]}" for k in bad.tolist()]
         log.warning(f"non-finite w_start in arm(s) {names}: recomputed on the CPU")
         COUNTERS.add("pfml_fi.recomputed_arms", int(bad.numel()))
         Wst_c, Wopt_c = _chain_arms(mt_all.cpu(), a_all.cpu(), wa[bad].cpu(), layout, to=dev)
         Wst[bad], Wopt[bad] = Wst_c, Wopt_c
-        still = ~_finite_arms(Wst_c, live)
+        still = ~portfolio.finite_arms(Wst_c, live)
         for k in bad[still].tolist():
             reasons[k] = "w_start stays non-finite on the CPU recursion"
             log.warning(f"arm {arms[k][0]}/{arms[k][1]}: {reasons[k]}")

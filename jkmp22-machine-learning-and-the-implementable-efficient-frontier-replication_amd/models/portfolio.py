@@ -401,6 +401,13 @@ def _chain_multi(mt_all: torch.Tensor, a_all: torch.Tensor, wa: torch.Tensor,
     return Wst, Wopt, ws.contiguous()
 
 
+def finite_arms(Wst: torch.Tensor, live: torch.Tensor) -> torch.Tensor:
+    """[A] bool: every live w_start of the arm is finite (Wst [A, B, N], live [B, N]): the
+    failure guard of the multi-portfolio stages."""
+    z = torch.zeros((), dtype=Wst.dtype, device=Wst.device)
+    return torch.isfinite(torch.where(live, Wst, z)).flatten(1).all(1)
+
+
 def pfml_weights(cfg: Config, chars: pd.DataFrame, barra: BarraCov, wealth: pd.DataFrame,
                  risk_free: pd.DataFrame, aims: pd.DataFrame, oos_months: np.ndarray,
                  device, mine_months: np.ndarray | None = None,

@@ -14,6 +14,7 @@ Stages (CLI names) and the reference script each one replaces:
     pfml-hps             PFML_hps.py
     pfml-best-hps        PFML_best_hps.py
     pfml-fi              (none: feature-theme importance, settings["fi"]; not in ``main``)
+    pfml-bmk             (none: the benchmark portfolios, settings["bmk"]; not in ``main``)
     pfml-ef              (none: the wealth x gamma frontier of settings["ef"]; not in ``main``)
 
 State flows in memory within one process; with ``checkpoint=True`` every stage also writes
@@ -61,6 +62,9 @@ log = get_logger("pipeline")
 MAIN_STAGES = ["prepare-data", "estimate-cov", "pfml-input", "pfml-search-coef",
                "pfml-hp-reals", "pfml-aim", "pfml-hps", "pfml-best-hps"]
 ALL_STAGES = ["get-additional-data", "sp500-subset"] + MAIN_STAGES + ["pfml-fi", "pfml-ef"]
+# stages run by name only, outside the key chain of ALL_STAGES (each a sibling, below): adding
+# one moves no other stage's key
+SIDE_STAGES = ["pfml-bmk"]
 
 # settings sections (and run options) each stage's output depends on (for resume keys);
 # keys chain, so a change invalidates the stage and everything downstream
@@ -81,11 +85,15 @@ _DEPS = {
     # feature importance: one such point plus the permuted arms (models/importance.py)
     "pfml-fi": ("fi", "pf_ml", "Transaction_Costs", "seed_no", "compat_mode", "precision",
                 "iterations", "pf", "mu", "lb_hor"),
+    # benchmark portfolios: one such point plus the prediction model and the solve chain
+    # (models/benchmarks.py)
+    "pfml-bmk": ("bmk", "rff", "pf_ml", "Transaction_Costs", "seed_no", "compat_mode",
+                 "precision", "iterations", "pf", "mu", "lb_hor"),
 }
 # stages outside the key chain: a sibling's key is its parent's chained key plus its own
 # dependency hash, and the chain runs on without it (pfml-fi was added in front of pfml-ef,
 # whose key - and with it every frontier checkpoint - stays what it was)
-_SIBLING_OF = {"pfml-fi": "pfml-best-hps"}
+_SIBLING_OF = {"pfml-fi": "pfml-best-hps", "pfml-bmk": "pfml-best-hps"}
 # stages whose artifacts are per rank (resume per shard)
 _SHARDED = ("pfml-input", "pfml-search-coef")
 # per-rank artifact payload versions (part of the done-marker key)
@@ -115,8 +123,8 @@ class Pipeline:
     def run(self, stages: list[str] | None = None) -> dict:
         stages = stages or MAIN_STAGES
         for st in stages:
-            if st not in ALL_STAGES:
-                raise ValueError(f"unknown stage {st!r}; choose from {ALL_STAGES}")
+            if st not in ALL_STAGES + SIDE_STAGES:
+                raise ValueError(f"unknown stage {st!r}; choose from {ALL_STAGES + SIDE_STAGES}")
         for st in stages:
             if self.checkpoint and self._all_done(st):
                 log.info(f"[{st}] up to date (resume)")
@@ -511,3 +519,24 @@ class Pipeline:
         log.info("feature importance:\n" + out["fi"][["cluster", "draw", "n_features", "r", "sd",
                                                        "tc", "obj", "obj_drop"]]
                  .to_string(index=False))
+
+    def _pfml_bmk(self):
+        """The benchmark portfolios (models/benchmarks.py): Portfolio-ML at the configured
+        wealth and gamma next to Markowitz-ML, the Static-ML arms of settings["bmk"], minimum
+        variance and 1/N, from the prepare-data and estimate-cov outputs alone."""
+        from .models import benchmarks
+        if self.env.world_size > 1:
+            raise RuntimeError(benchmarks.WORLD_ERROR)
+        self._load_common()
+        st = self.state
+        d = self.cfg.run.data_dir
+        out = benchmarks.benchmark_portfolios(self.cfg, st["chars"], st["barra"], st["wealth"],
+                                              st["risk_free"], self.device)
+        io.write_csv(out["bmk"], d, "bmk.csv")
+        io.write_csv(out["pf"], d, "bmk_pf.csv")
+        io.write_csv(out["hps"], d, "bmk_hps.csv")
+        st.update(bmk=out["bmk"], bmk_pf=out["pf"], bmk_hps=out["hps"])
+        if self.cfg.run.plots:
+            benchmarks.plot_benchmarks(out["bmk"], os.path.join(d, "plots"))
+        log.info("benchmark portfolios:\n" + out["bmk"][["type", "k", "u", "g", "r", "sd", "tc",
+                                                         "r_tc", "obj"]].to_string(index=False))
