@@ -398,7 +398,9 @@ __constant__ UpdRows kUpdRows = make_upd_rows();
 // stores, the hand-off words and z use plain accesses: a plain store keeps the line in the XCD's
 // L2 for the next panel's X phase and update, where a write-through (sc1) store drops it.  The
 // arithmetic is the general kernel's K = 1 path: the same bits.  The sync words are still
-// passed (zeroed by the launch): the back-transform reads the error word, which stays 0.
+// passed (zeroed by the cell's workgroup at entry, no memset before the launch): the
+// back-transform reads the error word, which stays 0.  z's rows >= 16 live in the padding column
+// of Vs between the start-up copy and the epilogue.
 template <bool TIMED, bool SOLO>
 __global__ __launch_bounds__(NTR) void band_coop_kernel(
     const double* __restrict__ SD, int64_t ldS, const double* __restrict__ Sr,
@@ -452,8 +454,11 @@ __global__ __launch_bounds__(NTR) void band_coop_kernel(
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), rsW,
                                           (unsigned)((p - A) * 8), 0, AUX);
   };
+  // (timed instances: the clock is read at entry, so slot 0 covers the start-up copy and panel
+  // 0, and the last mark follows the band epilogue, which slot 7 covers)
   long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   long long tlast = 0;
+  if (TIMED && threadIdx.x == 0) tlast = (long long)__builtin_amdgcn_s_memtime();
 #define COOP_TMARK(ph)                                                   \
   if (TIMED && threadIdx.x == 0) {                                       \
     const long long now = (long long)__builtin_amdgcn_s_memtime();       \
@@ -465,23 +470,68 @@ __global__ __launch_bounds__(NTR) void band_coop_kernel(
 
   // ---- A = S * scale (the lower block triangle incl. the diagonal blocks, zero padding),
   //      z = r * scale: row blocks gb = w (mod K)
+  //      A wave takes whole rows (rows wid and wid + 8 of each block: the row index is
+  //      wave-uniform, no division), its lanes the row's column pairs in chunks of 64.  CPB
+  //      (row, chunk) units form one batch: their 2 CPB 8-byte loads (ldS may be odd) are all
+  //      issued, at clamped addresses, before the first is used; the i < n, j < n masks are
+  //      selects behind the loads and a unit past the end is a dropped store.
+  if constexpr (SOLO) {
+    // (no memset before a solo launch: the cell's one workgroup zeroes its own sync words;
+    // nothing adds to them, and the back-transform and the host read the error word as 0)
+    if (t_ < COOP_SYNC) syncw[(int64_t)cell * COOP_SYNC + t_] = 0u;
+  }
   {
     const double* S = SD + cd.src;
     const double sc = cd.scale;
-    for (int gb = w; gb < nb; gb += K) {
-      const int wc = 8 * (gb + 1);                 // column pairs through the diagonal block
-      for (int e = t_; e < BB * wc; e += NTR) {
-        const int i = 16 * gb + e / wc, j = 2 * (e % wc);
+    constexpr int CPB = 8;
+    int b = 0, h = 0, c = 0;                       // block w + K b, row wid + 8 h, chunk c
+    while (w + K * b < nb) {
+      double x0[CPB], x1[CPB];
+      int ri[CPB], jc[CPB];
+      bool ok[CPB];
+#pragma unroll
+      for (int u = 0; u < CPB; ++u) {
+        const int gb = w + K * b;
+        const int i = 16 * gb + wid + 8 * h, jp = 64 * c + lane_;
+        ri[u] = i;
+        jc[u] = 2 * jp;
+        ok[u] = gb < nb && jp < 8 * (gb + 1);      // column pairs through the diagonal block
         const double* srow = S + (int64_t)min(i, n - 1) * ldS;
-        const double x = (i < n && j < n) ? srow[j] * sc : 0.0;
-        const double y = (i < n && j + 1 < n) ? srow[j + 1] * sc : 0.0;
-        st2((unsigned)((i * lda + j) * 8), true, x, y);
+        x0[u] = srow[min(2 * jp, n - 1)];
+        x1[u] = srow[min(2 * jp + 1, n - 1)];
+        if (++c >= (gb + 8) >> 3) {                // ceil(8 (gb + 1) / 64) chunks per row
+          c = 0;
+          if (++h == 2) {
+            h = 0;
+            ++b;
+          }
+        }
       }
-      if (t_ < BB && 16 * gb + t_ < n) stw(bw.z + 16 * gb + t_, Sr[cd.rsrc + 16 * gb + t_] * sc);
+#pragma unroll
+      for (int u = 0; u < CPB; ++u) {
+        const int i = ri[u], j = jc[u];
+        // (the loaded values pinned in registers here: without it the compiler sank the last
+        // load under its mask's branch and waited for it alone)
+        asm volatile("" : "+v"(x0[u]), "+v"(x1[u]));
+        const double x = (i < n && j < n) ? x0[u] * sc : 0.0;
+        const double y = (i < n && j + 1 < n) ? x1[u] * sc : 0.0;
+        st2((unsigned)((i * lda + j) * 8), ok[u], x, y);
+      }
+    }
+    if constexpr (SOLO) {
+      // z of the rows >= 16 (the ones the panels update) lives in the padding column of Vs,
+      // which no other code touches: global row g at Vs[g - 16][BB] (n <= BNMAX: g - 16 < BMP)
+      for (int g = t_; g < n; g += NTR) {
+        const double zv = Sr[cd.rsrc + g] * sc;
+        if (g < BB) stw(bw.z + g, zv);
+        else Vs[g - BB][BB] = zv;
+      }
+    } else {
+      for (int gb = w; gb < nb; gb += K)
+        if (t_ < BB && 16 * gb + t_ < n) stw(bw.z + 16 * gb + t_, Sr[cd.rsrc + 16 * gb + t_] * sc);
     }
   }
   cs.sync(true, &err_s);
-  if (TIMED && threadIdx.x == 0) tlast = (long long)__builtin_amdgcn_s_memtime();
 
   // ---- panel 0 (the QR workgroup): column block 0, rows 16.., then publish V_0, T_0
   auto publish_vt = [&](int mp) {
@@ -490,9 +540,17 @@ __global__ __launch_bounds__(NTR) void band_coop_kernel(
   };
   if (npan > 0 && qwg) {
     const int m0 = n - BB;
-    for (int e = t_; e < BMP * BB; e += NTR) {
-      const int i = e / BB, c = e % BB;
-      Vs[i][c] = (i < m0) ? A[(int64_t)(BB + i) * lda + c] : 0.0;
+    // (a thread's 16 loads, rows clamped, all in flight before the first LDS write)
+    double v[BMP * BB / NTR];
+#pragma unroll
+    for (int u = 0; u < BMP * BB / NTR; ++u) {
+      const int i = (t_ >> 4) + (NTR / BB) * u;
+      v[u] = A[(int64_t)(BB + min(i, m0 - 1)) * lda + (t_ & 15)];
+    }
+#pragma unroll
+    for (int u = 0; u < BMP * BB / NTR; ++u) {
+      const int i = (t_ >> 4) + (NTR / BB) * u;
+      Vs[i][t_ & 15] = (i < m0) ? v[u] : 0.0;
     }
     __syncthreads();
     band_panel_hh(A, lda, 0, BB, m0, Vs, Ws, &red[0][0], Ts, taus, bw.T, nullptr, Vs);
@@ -583,7 +641,9 @@ __global__ __launch_bounds__(NTR) void band_coop_kernel(
           const int row = i0 + 4 * r + g4;
           const double va = Vs[row][c16];
           Pp = mfma_f64_16x16x4(va, X[q][r], Pp);
-          const double zl = ldw(bw.z + r0 + min(row, m - 1));
+          double zl;                                 // (solo: z's LDS copy, row r0 + . - 16)
+          if constexpr (SOLO) zl = Vs[k0 + min(row, m - 1)][BB];
+          else zl = ldw(bw.z + r0 + min(row, m - 1));
           const double zb = (c16 == 0 && row < m) ? zl : 0.0;
           Pz = mfma_f64_16x16x4(va, zb, Pz);
         }
@@ -625,8 +685,26 @@ __global__ __launch_bounds__(NTR) void band_coop_kernel(
     }
     __syncthreads();
     if (t < BB) {
+      // (solo: the LDS reads of eight terms at a time first, then their part of the chain in
+      // the same order: two round trips, not one per term.  All 32 reads at once cost the solo
+      // instance scratch, and any batched form cost the general one 8 B more of it.)
       double s = 0.0;
-      for (int a = 0; a <= t; ++a) s = fma(Ts[a][t], red[1][a], s);
+      if constexpr (!SOLO) {
+        for (int a = 0; a <= t; ++a) s = fma(Ts[a][t], red[1][a], s);
+      }
+#pragma unroll
+      for (int a0 = 0; SOLO && a0 < BB; a0 += 8) {
+        double ta[8], ra[8];
+#pragma unroll
+        for (int a = 0; a < 8; ++a) {
+          ta[a] = Ts[a0 + a][t];
+          ra[a] = red[1][a0 + a];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int a = 0; a < 8; ++a) s = (a0 + a <= t) ? fma(ta[a], ra[a], s) : s;
+        __builtin_amdgcn_sched_barrier(0);
+      }
       zts[t] = s;
     }
     double4_t Mm = {0.0, 0.0, 0.0, 0.0};
@@ -643,7 +721,8 @@ __global__ __launch_bounds__(NTR) void band_coop_kernel(
           double s = 0.0;
 #pragma unroll
           for (int c = 0; c < BB; ++c) s = fma(Vs[i][c], zts[c], s);
-          stw(bw.z + r0 + i, ldw(bw.z + r0 + i) - s);
+          if constexpr (SOLO) Vs[k0 + i][BB] = Vs[k0 + i][BB] - s;
+          else stw(bw.z + r0 + i, ldw(bw.z + r0 + i) - s);
         }
         double4_t acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -858,9 +937,6 @@ __global__ __launch_bounds__(NTR) void band_coop_kernel(
     cs.sync(true, &err_s);
     COOP_TMARK(7)
   }
-  if (TIMED && threadIdx.x == 0 && w < 2)
-    for (int q = 0; q < TIM_WG; ++q) tim[timing_cell_slot(cell, w) + q] = tacc[q];
-#undef COOP_TMARK
   // ---- row-major lower band (the QR workgroup: it wrote the R blocks itself)
   if (qwg) {
     for (int e = t_; e < n * LS; e += NTR) {
@@ -868,19 +944,33 @@ __global__ __launch_bounds__(NTR) void band_coop_kernel(
       bw.LB[e] = (c >= 0) ? A[(int64_t)r * lda + c] : 0.0;
     }
   }
+  if constexpr (SOLO) {
+    // z's rows >= 16, final since their panel's phase C, leave the LDS once (the solve reads bw.z)
+    for (int g = BB + t_; g < n; g += NTR) stw(bw.z + g, Vs[g - BB][BB]);
+  }
+  if (TIMED) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the epilogue's stores are out)
+    COOP_TMARK(7)
+    if (threadIdx.x == 0 && w < 2)
+      for (int q = 0; q < TIM_WG; ++q) tim[timing_cell_slot(cell, w) + q] = tacc[q];
+  }
+#undef COOP_TMARK
 }
 
 }  // namespace
 
-// nwg workgroups (wgmap: cell << 8 | w << 4 | K - 1), the cells' sync words zeroed on the
-// stream first (a memset node under graph capture).
+// nwg workgroups (wgmap: cell << 8 | w << 4 | K - 1).  A general launch zeroes the cells' sync
+// words on the stream first (a memset node under graph capture); the solo instance zeroes them
+// itself (each cell's one workgroup, at entry), so a solo launch is the kernel alone.
 hipError_t band_reduce_launch(const RidgeLaunchArgs& a, hipStream_t st) {
   if (a.wgmap == nullptr || a.syncw == nullptr || a.nwg <= 0) return hipErrorInvalidValue;
-  const hipError_t e =
-      hipMemsetAsync(a.syncw, 0, (size_t)a.ncells * COOP_SYNC * sizeof(unsigned), st);
-  if (e != hipSuccess) return e;
   // nwg == ncells: every cell has K = 1, the solo instance (no hand-offs, plain stores)
   const bool solo = a.solo && a.nwg == a.ncells;
+  if (!solo) {
+    const hipError_t e =
+        hipMemsetAsync(a.syncw, 0, (size_t)a.ncells * COOP_SYNC * sizeof(unsigned), st);
+    if (e != hipSuccess) return e;
+  }
   const unsigned spin_max = a.spin_max ? a.spin_max : COOP_SPIN_MAX;
 #define COOP_LAUNCH(TIMED, SOLO)                                                             \
   hipLaunchKernelGGL((band_coop_kernel<TIMED, SOLO>), dim3(a.nwg), dim3(NTR), 0, st, a.SD,   \

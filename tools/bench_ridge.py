@@ -60,8 +60,10 @@ def timing(n=513):
         rg.ridge_launch(plan, d_desc, SD, Sr, lv, beta, d_wgmap=d_wg, timing=tim)
     torch.cuda.synchronize()
     allb = buf.cpu().numpy()
-    names = ["init_panel0", "U", "X_partials", "sync_wait", "C_sums_W", "update",
-             "lookahead_qr", "end_sync"]
+    # (slot 0 runs from kernel entry: the start-up copy A = S * scale and panel 0; slot 7 ends
+    # behind the row-major band epilogue)
+    names = ["startup_copy_panel0", "U", "X_partials", "sync_wait", "C_sums_W", "update",
+             "lookahead_qr", "end_sync_epilogue"]
     out = {"K": os.environ.get("PFML_COOP_K", "auto"), "cells": ncells}
     for w in (0, 1):
         t = allb[w * 8:(w + 1) * 8]
