@@ -22,6 +22,11 @@ generation and the headline benchmark.
                    (benchmark portfolios: Portfolio-ML next to Markowitz-ML, the Static-ML
                    arms, minimum variance and 1/N -> bmk.csv, bmk_pf.csv, bmk_hps.csv,
                    plots/benchmarks.png; same inputs as pfml-ef; one process; not part of `main`)
+    python -m pfml pfml-mp      --data-dir Data --device cuda
+                   [--set mp.K=12 --set mp.u=[1,0.5,0.25] --set mp.gbar=1]
+                   (Multiperiod-ML: Portfolio-ML next to the multi-period closed form on return
+                   predictions at horizons 1..K, one arm per u -> mp.csv, mp_pf.csv, mp_hps.csv;
+                   same inputs as pfml-ef; one process; not part of `main`)
     python -m pfml stages a,b,c  (several stages in one process)
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m pfml main ...   (RCCL, one rank/GPU)
 

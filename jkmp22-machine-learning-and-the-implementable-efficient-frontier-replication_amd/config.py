@@ -145,6 +145,10 @@ def _reference_settings() -> dict:
         # reference's pf.hps.static lists can be passed with --set)
         "bmk": {"l_vec": None, "p_vec": None,
                 "static": {"k": [1.0], "u": [1.0], "g": [0.0]}},
+        # Multiperiod-ML (models/multiperiod.py): the horizons K (None: pf.hps.m1.K), the arms'
+        # scales u on mu_hat, the fold's discount gbar, the prediction models' grid (None: as
+        # bmk's defaults)
+        "mp": {"K": None, "u": [1.0], "gbar": 1.0, "l_vec": None, "p_vec": None},
         "cov_set": {
             "industries": True,
             "obs": 252 * 10,
@@ -307,12 +311,12 @@ class Config:
         """Stable hash of (a subset of) the config, used to key stage artifacts."""
         doc = self.to_jsonable()
         # the whole-config hash keys the stages without a dependency list (and, chained,
-        # everything after them): settings["fi"] is read by pfml-fi alone and settings["bmk"] by
-        # pfml-bmk alone, which name them, and stay out, so the keys of every other stage are
-        # what they were before those stages existed
+        # everything after them): settings["fi"] is read by pfml-fi alone, settings["bmk"] by
+        # pfml-bmk alone and settings["mp"] by pfml-mp alone, which name them, and stay out, so
+        # the keys of every other stage are what they were before those stages existed
         if not sections:
             doc["settings"] = {k: v for k, v in doc["settings"].items()
-                               if k not in ("fi", "bmk")}
+                               if k not in ("fi", "bmk", "mp")}
         if sections:
             doc = {s: doc["settings"].get(s, doc["pf_set"].get(s, doc["run"].get(s)))
                    for s in sections}

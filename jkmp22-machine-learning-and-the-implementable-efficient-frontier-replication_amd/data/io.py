@@ -32,6 +32,10 @@ CSV_COLUMNS = {
                 "sr_gross", "tc", "r_tc", "sr", "obj", "reason"],
     "bmk_pf.csv": ["type", "k", "u", "g", "inv", "shorting", "turnover", "r", "tc", "eom_ret"],
     "bmk_hps.csv": ["hp_year", "g", "p", "l", "lambda", "val_mse"],
+    "mp.csv": ["type", "u", "n", "inv", "shorting", "turnover_notional", "r", "sd", "sr_gross",
+               "tc", "r_tc", "sr", "obj", "reason"],
+    "mp_pf.csv": ["type", "u", "inv", "shorting", "turnover", "r", "tc", "eom_ret"],
+    "mp_hps.csv": ["horizon", "hp_year", "g", "p", "l", "lambda", "val_mse"],
 }
 
 

@@ -86,14 +86,19 @@ def static_arms(cfg: Config) -> list:
     return arms
 
 
-def prediction_reals(plan: pin.S4Plan, cfg: Config, keep: np.ndarray):
+def prediction_reals(plan: pin.S4Plan, cfg: Config, keep: np.ndarray, targets=None):
     """The summands of the return-prediction model for every month of the plan and every g:
     (r [G, T, P] = Z'y, D [G, T, P, P] = Z'Z, yy [T] = y'y, ny [T] rows with a finite y, z:
     per distinct signal block, per month a [n_t, P] copy of Z_t for the months of ``keep``).
 
     Z_t: ``rff_features`` + ``standardize_signals`` at lag 0 over the month's signal universe
     with a vol table of ones (no 1 / vol row scale); y = ret_ld1 of the plan's batches.  A row
-    with a non-finite y is dropped from both sums.  D by the symmetric-mode GEMM."""
+    with a non-finite y is dropped from both sums.  D by the symmetric-mode GEMM.
+
+    ``targets`` [K, T, N] (``multiperiod.horizon_targets``: further regressands on the batches'
+    rows): a sixth result r_h [K, G, T, P] = Z'y_h of every horizon, one [P x N] [N x K] product
+    per month and g on the same Z (Z'Z is shared; the rows dropped for y are dropped for every
+    y_h)."""
     dev = plan.feats.device
     f64 = dict(dtype=torch.float64, device=dev)
     G, Gc, P, Pp, N, T = plan.G, plan.Gc, plan.P, plan.Pp, plan.N, len(plan.months)
@@ -105,6 +110,12 @@ def prediction_reals(plan: pin.S4Plan, cfg: Config, keep: np.ndarray):
     yy = torch.empty(T, **f64)
     ny = torch.empty(T, **f64)
     z = [[None] * T for _ in range(Gc)]
+    rh_out = None
+    if targets is not None:
+        if targets.dim() != 3 or tuple(targets.shape[1:]) != (T, N):
+            raise ValueError(f"prediction_reals: targets must be [K, {T}, {N}]")
+        Kh = int(targets.shape[0])
+        rh_out = torch.empty((Kh, G, T, P), **f64)
     keep_set = set(int(m) for m in keep)
     b0 = 0
     for bt in plan.batches:
@@ -124,12 +135,22 @@ def prediction_reals(plan: pin.S4Plan, cfg: Config, keep: np.ndarray):
             gemm_fused(Zy, Zy, Dt, trans_a=True, sym=True)
             d_out[g, sl] = Dt[:, :P, :P]
             r_out[g, sl] = (Zy * y[..., None]).sum(1)[:, :P]
+            if targets is not None:
+                Yt = targets[:, sl].to(**f64).permute(1, 2, 0).contiguous()      # [B, N, K]
+                Rh = torch.empty((B, Pp, Kh), **f64)
+                gemm_fused(Zy, Yt, Rh, trans_a=True)
+                rh_out[:, g, sl] = Rh[:, :P].permute(2, 0, 1)
+                del Yt, Rh
             for bi in kept:                     # copies: a view would pin the whole block
                 z[g][b0 + bi] = Z[bi, 0, : int(bt.ns[bi]), :P].clone()
             del Z, Zy, Dt
         b0 += B
     for g in range(Gc, G):                                  # one signal block (quirk Q1)
         r_out[g], d_out[g] = r_out[0], d_out[0]
+        if rh_out is not None:
+            rh_out[:, g] = rh_out[:, 0]
+    if rh_out is not None:
+        return r_out, d_out, yy, ny, z, rh_out
     return r_out, d_out, yy, ny, z
 
 

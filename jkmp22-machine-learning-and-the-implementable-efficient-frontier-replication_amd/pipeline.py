@@ -15,6 +15,7 @@ Stages (CLI names) and the reference script each one replaces:
     pfml-best-hps        PFML_best_hps.py
     pfml-fi              (none: feature-theme importance, settings["fi"]; not in ``main``)
     pfml-bmk             (none: the benchmark portfolios, settings["bmk"]; not in ``main``)
+    pfml-mp              (none: Multiperiod-ML, settings["mp"]; not in ``main``)
     pfml-ef              (none: the wealth x gamma frontier of settings["ef"]; not in ``main``)
 
 State flows in memory within one process; with ``checkpoint=True`` every stage also writes
@@ -64,7 +65,7 @@ MAIN_STAGES = ["prepare-data", "estimate-cov", "pfml-input", "pfml-search-coef",
 ALL_STAGES = ["get-additional-data", "sp500-subset"] + MAIN_STAGES + ["pfml-fi", "pfml-ef"]
 # stages run by name only, outside the key chain of ALL_STAGES (each a sibling, below): adding
 # one moves no other stage's key
-SIDE_STAGES = ["pfml-bmk"]
+SIDE_STAGES = ["pfml-bmk", "pfml-mp"]
 
 # settings sections (and run options) each stage's output depends on (for resume keys);
 # keys chain, so a change invalidates the stage and everything downstream
@@ -89,11 +90,16 @@ _DEPS = {
     # (models/benchmarks.py)
     "pfml-bmk": ("bmk", "rff", "pf_ml", "Transaction_Costs", "seed_no", "compat_mode",
                  "precision", "iterations", "pf", "mu", "lb_hor"),
+    # Multiperiod-ML: one such point plus a prediction model per horizon, the horizon fold and
+    # the offset weight chain (models/multiperiod.py)
+    "pfml-mp": ("mp", "rff", "pf_ml", "Transaction_Costs", "seed_no", "compat_mode",
+                "precision", "iterations", "pf", "mu", "lb_hor"),
 }
 # stages outside the key chain: a sibling's key is its parent's chained key plus its own
 # dependency hash, and the chain runs on without it (pfml-fi was added in front of pfml-ef,
 # whose key - and with it every frontier checkpoint - stays what it was)
-_SIBLING_OF = {"pfml-fi": "pfml-best-hps", "pfml-bmk": "pfml-best-hps"}
+_SIBLING_OF = {"pfml-fi": "pfml-best-hps", "pfml-bmk": "pfml-best-hps",
+               "pfml-mp": "pfml-best-hps"}
 # stages whose artifacts are per rank (resume per shard)
 _SHARDED = ("pfml-input", "pfml-search-coef")
 # per-rank artifact payload versions (part of the done-marker key)
@@ -540,3 +546,22 @@ class Pipeline:
             benchmarks.plot_benchmarks(out["bmk"], os.path.join(d, "plots"))
         log.info("benchmark portfolios:\n" + out["bmk"][["type", "k", "u", "g", "r", "sd", "tc",
                                                          "r_tc", "obj"]].to_string(index=False))
+
+    def _pfml_mp(self):
+        """Multiperiod-ML (models/multiperiod.py): Portfolio-ML at the configured wealth and
+        gamma next to the Multiperiod-ML arms of settings["mp"], from the prepare-data and
+        estimate-cov outputs alone."""
+        from .models import multiperiod
+        if self.env.world_size > 1:
+            raise RuntimeError(multiperiod.WORLD_ERROR)
+        self._load_common()
+        st = self.state
+        d = self.cfg.run.data_dir
+        out = multiperiod.multiperiod_portfolios(self.cfg, st["chars"], st["barra"],
+                                                 st["wealth"], st["risk_free"], self.device)
+        io.write_csv(out["mp"], d, "mp.csv")
+        io.write_csv(out["pf"], d, "mp_pf.csv")
+        io.write_csv(out["hps"], d, "mp_hps.csv")
+        st.update(mp=out["mp"], mp_pf=out["pf"], mp_hps=out["hps"])
+        log.info("multiperiod portfolios:\n" + out["mp"][["type", "u", "r", "sd", "tc", "r_tc",
+                                                          "obj"]].to_string(index=False))
